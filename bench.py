@@ -28,7 +28,16 @@ region starts.
   1 pairwise count_and/or/xor/sub + materialised ops on 1e9-bit vectors, rotating over distinct vector pairs so
     that nothing is served from the 256 MB Infinity Cache;  3 rank/select, 10 M queries on a 4e9-bit vector;
   4 combine_or over 4096 x 4e9-bit sparse vectors, block-range sharded over the ranks / members.
-The default run (config 2, one GPU) appends their one-line summaries as "other_configs" (--no-others skips them).
+A --full run of config 2 on one GPU appends their one-line summaries as "other_configs" (--no-others skips them).
+
+A plain run of config 2 does only what its headline figure needs: build the resident collection, warm up, time --steps
+steps, print the line.  --full adds everything else it measures: the CPU baselines, the kernel-alone roofline and
+per-rank figures, the 1/8 shard probe, the materialised combine_and, the host -> device upload, weak scaling and
+"other_configs".  The --no-* switches prune legs of a --full run.
+
+--dump-outputs DIR (config 2): after the timed steps, write what the timed path computed in its last step -- the
+per-arg-group counts a caller of the pipeline receives -- as DIR/counts.npy (float64).  Inputs come from the fixed
+SEED, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -430,6 +439,14 @@ def event_avg_ms(fn, reps, ctx):
     return ctx.timer_stop_ms() / reps
 
 
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (counts up to 2^53 stay exact)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def gather_floats(x: float, env):
     torch = env.torch
     t = torch.tensor([x], dtype=torch.float64, device="cpu" if env.one_dev else "cuda")
@@ -538,21 +555,26 @@ def run_headline(args, env, cpu):
             if use_dist:
                 dist.all_reduce(counts)                  # RCCL: 8 bytes per arg-group, same stream as the kernel
         dt, ev_ms = timed_region(step, args.steps, args.warmup, env)
-        total = int(counts.item())
-        k_ms = event_avg_ms(kernel, max(5, min(args.steps, 20)), ctx)      # the kernel alone
-        ar_us = None
-        if use_dist:
-            ar_us = event_avg_ms(lambda: dist.all_reduce(counts), 20, ctx) * 1e3
-        return {"dt": dt, "ev_ms": ev_ms, "count": total, "op_bytes": op_bytes, "k_ms": k_ms, "ar_us": ar_us,
+        out = counts.cpu().numpy()                       # the last timed step's counts, before any later launch reuses `counts`
+        total = int(out[0])
+        k_ms = ar_us = None
+        if args.full:
+            k_ms = event_avg_ms(kernel, max(5, min(args.steps, 20)), ctx)      # the kernel alone
+            if use_dist:
+                ar_us = event_avg_ms(lambda: dist.all_reduce(counts), 20, ctx) * 1e3
+        return {"dt": dt, "ev_ms": ev_ms, "count": total, "out": out, "op_bytes": op_bytes, "k_ms": k_ms, "ar_us": ar_us,
                 "build_s": t_build, "blocks": hi - lo, "plan": pipe.describe(), "nlaunch": pipe.launches(),
                 "stat0": vecs[0].calc_stat(), "mem": ctx.mem_used(), "pipe": pipe, "vecs": vecs, "prep_ms": prep_ms}
 
     main = run_mode(scaling)
-    k_all = gather_floats(main["k_ms"], env)
-    bytes_all = gather_floats(float(main["op_bytes"]), env)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"counts": main["out"]})
+    if args.full:
+        k_all = gather_floats(main["k_ms"], env)
+        bytes_all = gather_floats(float(main["op_bytes"]), env)
     # 1-GPU shard efficiency: the 1/8 block range of the same collection, time x 8 vs the full time
     shard_eff = None
-    if world == 1 and scaling == "strong" and not args.no_shard_probe and not args.independent:
+    if args.full and world == 1 and scaling == "strong" and not args.no_shard_probe and not args.independent:
         lo, hi = bm.shard_range(nblocks_full, 0, 8)
         pipe = main["pipe"]
         t_sh = event_avg_ms(lambda: agg.run_counts_dev(pipe, counts.data_ptr(), lo, hi), 20, ctx)
@@ -566,7 +588,7 @@ def run_headline(args, env, cpu):
     # the materialised form of the same aggregation: aggregator::combine_and (BASELINE configs[2] names "combine_and + count"):
     # the WHOLE host call (row build, kernel, result layout), result stored with opt_compress (src/bmaggregator.h:1210)
     mat = None
-    if world == 1 and scaling == "strong" and not args.no_others and not args.independent:
+    if args.full and world == 1 and scaling == "strong" and not args.no_others and not args.independent:
         ts = []
         for _ in range(4):
             ctx.synchronize(); t0 = time.perf_counter()
@@ -582,7 +604,7 @@ def run_headline(args, env, cpu):
                        "k_agg_and_sub, result kinds + layout); bytes = operand blocks + 8,192 B per stored result block"}
     # host -> device: what the boundary costs when the operands start on the host (SURVEY section 8(d) "separately report H2D upload time")
     h2d = None
-    if world == 1 and scaling == "strong" and not args.no_others and not args.independent:
+    if args.full and world == 1 and scaling == "strong" and not args.no_others and not args.independent:
         try:
             uv = main["vecs"][1]
             kinds, offs, bits, gaps = uv.block_table()
@@ -607,7 +629,7 @@ def run_headline(args, env, cpu):
             h2d = {"error": str(e)}
     weak = None
     del main["pipe"], main["vecs"]
-    if world > 1 and scaling == "strong" and not args.no_weak:
+    if args.full and world > 1 and scaling == "strong" and not args.no_weak:
         ctx.trim()
         w = run_mode("weak")
         weak = {"value": round(world * args.nvec * args.nbits * args.steps / w["dt"] / 1e9, 2), "unit": "Gbit/s",
@@ -619,12 +641,6 @@ def run_headline(args, env, cpu):
         return None
     bits_per_step = args.nvec * args.nbits * (world if scaling == "weak" else 1)
     value = bits_per_step * args.steps / main["dt"] / 1e9
-    achieved = main["op_bytes"] / (main["k_ms"] * 1e-3) / 1e9
-    # the PMC figure belongs to the headline data set on one GPU (density 10 %, data set A, 6 launch windows): any other
-    # density / data set / shard runs another kernel or another launch plan and carries no traffic figure
-    headline = args.density_q16 == 6554 and not args.independent and world == 1
-    traffic, tsrc, _ = traffic_file("traffic_latest.json", kernel=main["plan"], workload=f"agg_and_count_{args.nvec}x{args.nbits}") if headline else (None, None, {})
-    if traffic is not None and main["nlaunch"] != 6: traffic, tsrc = None, None
     res = {
         "metric": METRIC, "value": round(value, 2), "unit": "Gbit/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(main["dt"] / args.steps * 1e3, 4), "higher_is_better": True,
@@ -639,28 +655,35 @@ def run_headline(args, env, cpu):
                    "blocks_per_rank": main["blocks"], "result_count": main["count"],
                    "build_seconds": round(main["build_s"], 2), "hbm_resident_bytes": main["mem"],
                    "prepared_collection_ms": None if main["prep_ms"] is None else round(main["prep_ms"], 2)},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
-                     "kernel": main["plan"], "launches_per_step": main["nlaunch"],
-                     "algorithmic_bytes_per_launch": main["op_bytes"] // main["nlaunch"],
-                     "avg_launch_ms": round(main["k_ms"] / main["nlaunch"], 4),
-                     "algorithmic_bytes_per_step": main["op_bytes"], "kernel_ms_per_step": round(main["k_ms"], 4),
-                     "scope": "rank 0's GPU",
-                     "timing": "hipEvent pair on the launch stream around back-to-back passes of the kernel alone (a pass = "
-                               "launches_per_step launches over equal column windows); avg_launch_ms = pass time / launches, "
-                               "inter-launch gaps included"},
-        "per_rank": {"kernel_ms": [round(x, 4) for x in k_all],
-                     "GBps": [round(b / (k * 1e-3) / 1e9, 1) for b, k in zip(bytes_all, k_all)],
-                     "allreduce_us": None if main["ar_us"] is None else round(main["ar_us"], 1),
-                     "rccl_ranks": env.rccl_ranks(),
-                     "step_event_ms": round(main["ev_ms"] / args.steps, 4)},
     }
-    if args.independent:
-        # data set B: the AND dies after a few operands and the kernel stops reading a column there (the reference's digest
-        # exit); full-read bytes over an early-exit time is not a bandwidth: report time and rate only
-        res["roofline"].update({"achieved": None, "frac": None, "per_rank_note": "early exit: bytes actually read are not the full operand bytes",
-                                "note": "early-exit data set: time and Gbit/s of LOGICAL operand bits only; no bandwidth figure"})
-        res["per_rank"]["GBps"] = None
+    if args.full:
+        achieved = main["op_bytes"] / (main["k_ms"] * 1e-3) / 1e9
+        # the PMC figure belongs to the headline data set on one GPU (density 10 %, data set A, 6 launch windows): any other
+        # density / data set / shard runs another kernel or another launch plan and carries no traffic figure
+        headline = args.density_q16 == 6554 and not args.independent and world == 1
+        traffic, tsrc, _ = traffic_file("traffic_latest.json", kernel=main["plan"], workload=f"agg_and_count_{args.nvec}x{args.nbits}") if headline else (None, None, {})
+        if traffic is not None and main["nlaunch"] != 6: traffic, tsrc = None, None
+        res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": tsrc,
+                           "kernel": main["plan"], "launches_per_step": main["nlaunch"],
+                           "algorithmic_bytes_per_launch": main["op_bytes"] // main["nlaunch"],
+                           "avg_launch_ms": round(main["k_ms"] / main["nlaunch"], 4),
+                           "algorithmic_bytes_per_step": main["op_bytes"], "kernel_ms_per_step": round(main["k_ms"], 4),
+                           "scope": "rank 0's GPU",
+                           "timing": "hipEvent pair on the launch stream around back-to-back passes of the kernel alone (a pass = "
+                                     "launches_per_step launches over equal column windows); avg_launch_ms = pass time / launches, "
+                                     "inter-launch gaps included"}
+        res["per_rank"] = {"kernel_ms": [round(x, 4) for x in k_all],
+                           "GBps": [round(b / (k * 1e-3) / 1e9, 1) for b, k in zip(bytes_all, k_all)],
+                           "allreduce_us": None if main["ar_us"] is None else round(main["ar_us"], 1),
+                           "rccl_ranks": env.rccl_ranks(),
+                           "step_event_ms": round(main["ev_ms"] / args.steps, 4)}
+        if args.independent:
+            # data set B: the AND dies after a few operands and the kernel stops reading a column there (the reference's digest
+            # exit); full-read bytes over an early-exit time is not a bandwidth: report time and rate only
+            res["roofline"].update({"achieved": None, "frac": None, "per_rank_note": "early exit: bytes actually read are not the full operand bytes",
+                                    "note": "early-exit data set: time and Gbit/s of LOGICAL operand bits only; no bandwidth figure"})
+            res["per_rank"]["GBps"] = None
     if shard_eff:
         res["shard_1of8_on_one_gpu"] = shard_eff
     if mat:
@@ -735,30 +758,33 @@ def run_headline_group(args):
             cnt = step()
         sync_all()
         dt = time.perf_counter() - t0
-        k_ms = [0.0] * n; x_ms = [0.0] * n
-        reps = max(5, min(args.steps, 20))
-        for _ in range(reps):                            # per-member device times (HIP events on the member streams)
-            step()
-            k_ms = [a + b for a, b in zip(k_ms, pipe.last_ms())]
-            x_ms = [a + b for a, b in zip(x_ms, pipe.last_exchange_ms())]
-        k_ms = [a / reps for a in k_ms]; x_ms = [a / reps for a in x_ms]
+        k_ms = x_ms = None
+        if args.full:
+            k_ms = [0.0] * n; x_ms = [0.0] * n
+            reps = max(5, min(args.steps, 20))
+            for _ in range(reps):                        # per-member device times (HIP events on the member streams)
+                step()
+                k_ms = [a + b for a, b in zip(k_ms, pipe.last_ms())]
+                x_ms = [a + b for a, b in zip(x_ms, pipe.last_exchange_ms())]
+            k_ms = [a / reps for a in k_ms]; x_ms = [a / reps for a in x_ms]
         plan, nlaunch = pipe.describe(0)
-        r = {"dt": dt, "count": int(cnt[0]), "k_ms": k_ms, "x_ms": x_ms, "bytes": pipe.operand_bytes(), "plan": plan,
+        r = {"dt": dt, "count": int(cnt[0]), "out": cnt, "k_ms": k_ms, "x_ms": x_ms, "bytes": pipe.operand_bytes(), "plan": plan,
              "nlaunch": nlaunch, "build_s": t_build, "stat0": vecs[0].info(),
              "ranges": [grp.shard_range((nbits + 65535) // 65536, m) for m in range(n)]}
         del pipe, vecs
         return r
 
     main = run_mode(scaling)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"counts": main["out"]})
     weak = None
-    if scaling == "strong" and not args.no_weak:
+    if args.full and scaling == "strong" and not args.no_weak:
         w = run_mode("weak")
         weak = {"value": round(n * args.nvec * args.nbits * args.steps / w["dt"] / 1e9, 2), "unit": "Gbit/s",
                 "ms_per_step": round(w["dt"] / args.steps * 1e3, 4), "result_count": w["count"],
                 "note": f"{args.nvec} vectors of {n} x {args.nbits} bits: every member holds a {args.nbits}-bit share of each"}
     bits_per_step = args.nvec * args.nbits * (n if scaling == "weak" else 1)
     value = bits_per_step * args.steps / main["dt"] / 1e9
-    achieved = main["bytes"][0] / (main["k_ms"][0] * 1e-3) / 1e9
     c = main["stat0"]["counts"]
     res = {
         "metric": METRIC, "value": round(value, 2), "unit": "Gbit/s", "n_gpus": n, "steps": args.steps,
@@ -771,21 +797,23 @@ def run_headline_group(args):
                    "sharding": "bmx_group: member m holds blocks bmx_group_shard_range(nblocks, m) of every vector",
                    "member_block_ranges": main["ranges"], "devices": devices, "result_count": main["count"],
                    "build_seconds": round(main["build_s"], 2)},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "kernel": main["plan"],
-                     "launches_per_step": main["nlaunch"], "algorithmic_bytes_per_launch": main["bytes"][0] // max(main["nlaunch"], 1),
-                     "avg_launch_ms": round(main["k_ms"][0] / max(main["nlaunch"], 1), 4),
-                     "algorithmic_bytes_per_step": main["bytes"][0], "kernel_ms_per_step": round(main["k_ms"][0], 4),
-                     "scope": "member 0's GPU",
-                     "timing": "hipEvent pair on member 0's stream around its launches of one bmx_gpipeline_run_counts call, "
-                               "averaged over the calls after the timed region"},
-        "per_rank": {"kernel_ms": [round(x, 4) for x in main["k_ms"]],
-                     "GBps": [round(b / (k * 1e-3) / 1e9, 1) if k > 0 else None for b, k in zip(main["bytes"], main["k_ms"])],
-                     "allreduce_us": round(max(main["x_ms"]) * 1e3, 1), "rccl_ranks": rccl_ranks,
-                     "exchange_us_per_member": [round(x * 1e3, 1) for x in main["x_ms"]],
-                     "note": "allreduce_us = device time from the end of a member's kernel to the end of the exchange (it "
-                             "includes waiting for the slowest member)"},
     }
+    if args.full:
+        achieved = main["bytes"][0] / (main["k_ms"][0] * 1e-3) / 1e9
+        res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "kernel": main["plan"],
+                           "launches_per_step": main["nlaunch"], "algorithmic_bytes_per_launch": main["bytes"][0] // max(main["nlaunch"], 1),
+                           "avg_launch_ms": round(main["k_ms"][0] / max(main["nlaunch"], 1), 4),
+                           "algorithmic_bytes_per_step": main["bytes"][0], "kernel_ms_per_step": round(main["k_ms"][0], 4),
+                           "scope": "member 0's GPU",
+                           "timing": "hipEvent pair on member 0's stream around its launches of one bmx_gpipeline_run_counts call, "
+                                     "averaged over the calls after the timed region"}
+        res["per_rank"] = {"kernel_ms": [round(x, 4) for x in main["k_ms"]],
+                           "GBps": [round(b / (k * 1e-3) / 1e9, 1) if k > 0 else None for b, k in zip(main["bytes"], main["k_ms"])],
+                           "allreduce_us": round(max(main["x_ms"]) * 1e3, 1), "rccl_ranks": rccl_ranks,
+                           "exchange_us_per_member": [round(x * 1e3, 1) for x in main["x_ms"]],
+                           "note": "allreduce_us = device time from the end of a member's kernel to the end of the exchange (it "
+                                   "includes waiting for the slowest member)"}
     if one_dev:
         res["test_hook"] = f"{ONE_DEV_HOOK}=1: all members on device 0; timings mean nothing"
     res["rccl_ranks"] = rccl_ranks                              # (also under per_rank) printed whatever the exchange turned out to be
@@ -1578,9 +1606,16 @@ def main():
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--queries", type=int, default=10_000_000)
     ap.add_argument("--or-vecs", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="config 2: also run the CPU baselines, roofline / per-rank kernel figures, side probes, weak scaling and other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="config 2: write the last timed step's counts to DIR/counts.npy (float64)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs is implemented for --config 2")
     launched = "RANK" in os.environ and "MASTER_PORT" in os.environ
     if args.gpus > 1 and not launched:
         if args.launcher == "torchrun":
@@ -1606,7 +1641,7 @@ def main():
         sys.exit(2)
     single = int(os.environ.get("WORLD_SIZE", "1")) == 1
     cpu = None
-    if args.config == 2 and single and not args.no_cpu:
+    if args.config == 2 and single and args.full and not args.no_cpu:
         cpu = headline_cpu(args)                         # before torch / HIP are loaded into this process
     env = Env(args).setup()
     if args.config == 0:
@@ -1620,7 +1655,7 @@ def main():
     else:
         res = run_headline(args, env, cpu)
         standard = (args.nvec == 256 and args.nbits == NBITS_1G and args.density_q16 == 6554 and not args.independent)
-        if res is not None and single and standard and not args.no_others:
+        if res is not None and single and standard and args.full and not args.no_others:
             others = {}
             for name, fn in (("configs[0]", lambda: run_plumbing(args, env)),
                              ("configs[1]", lambda: run_pairwise(args, env, quick=True)),

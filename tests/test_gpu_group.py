@@ -422,7 +422,7 @@ def test_bench_plain_gpus2_uses_two_members():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"): env.pop(k, None)
     nbits = 40 * 65536 + 99
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--nvec", "16", "--nbits", str(nbits),
-                          "--steps", "3", "--warmup", "1", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
+                          "--steps", "3", "--warmup", "1", "--no-cpu", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -441,6 +441,30 @@ def test_bench_plain_gpus2_uses_two_members():
         assert out.returncode != 0 and not any(l.startswith("{") for l in out.stdout.splitlines())
 
 
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_dumps_the_last_step(tmp_path, gpus):
+    """a plain run (no --full) prints the headline fields and none of the side legs; --dump-outputs writes the counts of the
+    last timed step as float64, equal to the oracle's count (--gpus 2: the group path through the one-device hook)"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ); env["BMX_BENCH_TEST_ONE_DEVICE"] = "1"
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"): env.pop(k, None)
+    nbits = 40 * 65536 + 99
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--nvec", "16", "--nbits", str(nbits),
+                          "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["n_gpus"] == gpus and j["steps"] == 4 and j["ms_per_step"] > 0 and j["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"): assert k in j
+    for k in ("cpu_baseline", "other_configs", "roofline", "per_rank", "weak_scaling", "shard_1of8_on_one_gpu", "h2d_upload"):
+        assert k not in j, k
+    got = np.load(tmp_path / "counts.npy")
+    import oracle
+    P = oracle.port()
+    vecs = [P.import_words(P.gen_words(SEED, v, 6554, nbits, with_common=True), True, nbits) for v in range(16)]
+    assert got.dtype == np.float64 and got.tolist() == [float(P.pipeline_counts([(vecs, [])])[0])] == [float(j["config"]["result_count"])]
+
+
 def test_bench_gpus8_through_the_one_device_hook():
     """the 8-GPU invocations the driver will make, on ONE device (test hook: 8 members of a bmx_group on device 0): the headline
     `bench.py --gpus 8` and `bench.py --config 4 --gpus 8` must run, say n_gpus 8, print exchange / rccl_ranks / rccl_error
@@ -451,7 +475,7 @@ def test_bench_gpus8_through_the_one_device_hook():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"): env.pop(k, None)
     nbits = 203 * 65536 + 99
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--nvec", "16", "--nbits", str(nbits),
-                          "--steps", "3", "--warmup", "1", "--no-cpu", "--no-weak"], env=env, capture_output=True, text=True, timeout=900)
+                          "--steps", "3", "--warmup", "1", "--no-cpu", "--no-weak", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 8 and j["mode"] == "group" and len(j["per_rank"]["kernel_ms"]) == 8

@@ -29,18 +29,18 @@ stats_of() {  # stats_of <name> <command...>
   rm -rf /tmp/ks; ( cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/ks -o s -f csv -- "$@" > $R/$O/${name}_under_rocprof.txt 2>> $R/$O/err.txt )
   cp $(find /tmp/ks -name "*kernel_stats.csv" | head -1) $O/kernel_stats_$name.csv
 }
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 ( time timeout 2400 python -m pytest tests -q -m gpu > $O/pytest.txt 2>&1 ) 2> $O/pytest_time.txt; echo "pytest gpu rc=$?" > $O/rc.txt
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" >> $O/rc.txt
-( time timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt
+( time timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench_time.txt
 for c in 0 1 3 4; do timeout 600 python bench.py --config $c > $O/bench_config$c.json 2>> $O/err.txt; done
 timeout 600 python bench.py --config 1 --density-q16 655 > $O/bench_config1_1pct.json 2>> $O/err.txt
 timeout 600 python bench.py --config 1 --density-q16 32768 > $O/bench_config1_50pct.json 2>> $O/err.txt
 timeout 600 python bench.py --config 3 --density-q16 655 > $O/bench_config3_1pct.json 2>> $O/err.txt
-for dq in 328 197 66; do timeout 600 python bench.py --density-q16 $dq --no-prepare --no-cpu --no-others --no-shard-probe > $O/bench_dq${dq}_first_call.json 2>> $O/err.txt; done
-for dq in 197 66; do timeout 600 python bench.py --density-q16 $dq --no-cpu --no-others --no-shard-probe > $O/bench_dq${dq}_prepared.json 2>> $O/err.txt; done
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu --no-others > $O/bench_torchrun1.json 2> $O/bench_torchrun1.err
-BMX_BENCH_TEST_ONE_DEVICE=1 timeout 600 python bench.py --gpus 8 --nvec 64 --steps 5 --warmup 2 --no-cpu > $O/bench_group8_hook.json 2>> $O/err.txt
+for dq in 328 197 66; do timeout 600 python bench.py --full --density-q16 $dq --no-prepare --no-cpu --no-others --no-shard-probe > $O/bench_dq${dq}_first_call.json 2>> $O/err.txt; done
+for dq in 197 66; do timeout 600 python bench.py --full --density-q16 $dq --no-cpu --no-others --no-shard-probe > $O/bench_dq${dq}_prepared.json 2>> $O/err.txt; done
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 20 --warmup 3 --full --no-cpu --no-others > $O/bench_torchrun1.json 2> $O/bench_torchrun1.err
+BMX_BENCH_TEST_ONE_DEVICE=1 timeout 600 python bench.py --gpus 8 --nvec 64 --steps 5 --warmup 2 --full --no-cpu > $O/bench_group8_hook.json 2>> $O/err.txt
 timeout 600 python tools/bench_small.py > $O/bench_small.log 2>> $O/err.txt
 timeout 600 python tools/bench_scanner.py > $O/bench_scanner.log 2>> $O/err.txt
 timeout 600 python tools/bench_shift.py > $O/bench_shift.log 2>> $O/err.txt
