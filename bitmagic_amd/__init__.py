@@ -13,6 +13,8 @@ argument meaning and error behaviour), layered on the C-ABI of include/bmx.h:
       select(rank, pos, rs)         :5350           bvector.select(rank, rs) -> (found, pos)
     bm::bit_import_u32             src/bmbvimport.h bit_import_u32(ctx, words, optimize)
     bm::count_and/or/xor/sub       src/bmalgo.h     count_and(a, b) ...
+    bm::distance_operation         src/bmalgo_impl.h:766  distance_operation(a, b, metrics)
+    similarity_batch::calculate    src/bmalgo_similarity.h  distance_matrix(A, B, metrics)  (all pairs, one call)
     bm::aggregator<bvector<>>      src/bmaggregator.h:120
       add / reset / combine_or / combine_and /      aggregator.add / reset / combine_or /
       combine_and_sub                               combine_and / combine_and_sub
@@ -34,13 +36,16 @@ from .sharding import shard_range, allreduce_counts  # noqa: F401
 
 NULL, FULL, BIT, GAP = 0, 1, 2, 3
 AND, OR, XOR, SUB = 0, 1, 2, 3
+# bm::distance_metric (src/bmalgo_impl.h:57-66; the set_operation codes of src/bmconst.h:175-182)
+COUNT_AND, COUNT_XOR, COUNT_OR, COUNT_SUB_AB, COUNT_SUB_BA, COUNT_A, COUNT_B = 6, 7, 8, 9, 10, 11, 12
 BLOCK_WORDS, BLOCK_BITS = 2048, 65536
 opt_none, opt_compress = 0, 3        # bvector::optmode (src/bm.h:129-135)
 ID_MAX = 0xFFFFFFFF                  # bm::id_max (src/bmconst.h:109)
 ID_MAX64 = 0xFFFFFFFFFFFFFFFF
 
 __all__ = ["context", "bvector", "aggregator", "slice_scanner", "rs_index", "group", "gbvector", "gaggregator", "gpipeline", "bit_import_u32", "count_and", "count_or",
-           "count_xor", "count_sub", "BmxError", "simd_version", "device_count", "agg_run_options",
+           "count_xor", "count_sub", "distance_operation", "distance_matrix", "distance_matrix_dev",
+           "COUNT_AND", "COUNT_XOR", "COUNT_OR", "COUNT_SUB_AB", "COUNT_SUB_BA", "COUNT_A", "COUNT_B", "BmxError", "simd_version", "device_count", "agg_run_options",
            "agg_opt_only_counts", "agg_opt_bvect_and_counts", "agg_opt_disable_bvects_and_counts"]
 
 
@@ -415,6 +420,68 @@ def count_and(a, b): return _count_op2(AND, a, b)      # src/bmalgo.h:49
 def count_or(a, b): return _count_op2(OR, a, b)        # :149
 def count_xor(a, b): return _count_op2(XOR, a, b)      # :81
 def count_sub(a, b): return _count_op2(SUB, a, b)      # :115
+
+
+def _metrics(metrics):
+    m = [int(x) for x in metrics]
+    return (C.c_int * max(len(m), 1))(*m), len(m)
+
+
+def distance_operation(a: bvector, b: bvector, metrics) -> list:
+    """bm::distance_operation (src/bmalgo_impl.h:766): every metric of `metrics` (COUNT_*) of the pair (a, b), from ONE pass
+    over both vectors"""
+    arr, n = _metrics(metrics)
+    out = (C.c_uint64 * max(n, 1))()
+    check(lib().bmx_distance(a.ctx._h, a._h, b._h, arr, n, out))
+    return [int(out[k]) for k in range(n)]
+
+
+def _list_ctx(*lists):
+    for lst in lists:
+        for v in lst or ():
+            if v is not None:
+                return v.ctx
+    return None
+
+
+def _handles_opt(vecs):
+    arr = (C.c_void_p * max(len(vecs), 1))()
+    for i, v in enumerate(vecs):
+        arr[i] = None if v is None else v._h
+    return arr
+
+
+def distance_matrix(A, B=None, metrics=(COUNT_AND,), ctx: "context | None" = None) -> np.ndarray:
+    """all pairs: out[k, i, j] = metric k of (A[i], B[j]) as uint64, shape (len(metrics), len(A), len(B)).  B=None: the
+    symmetric matrix of A with itself.  None entries are empty vectors.  One device call for the whole matrix."""
+    A = list(A)
+    Bl = None if B is None else list(B)
+    nb = len(A) if Bl is None else len(Bl)
+    arr, n = _metrics(metrics)
+    out = np.zeros((n, len(A), nb), np.uint64)
+    ctx = ctx or _list_ctx(A, Bl)
+    if ctx is None:
+        if len(A) and nb:
+            raise ValueError("distance_matrix: every vector is None; pass ctx")
+        return out
+    check(lib().bmx_distance_matrix(ctx._h, _handles_opt(A), len(A), None if Bl is None else _handles_opt(Bl), nb, arr, n,
+                                    _ptr(out) if out.size else None))
+    return out
+
+
+def distance_matrix_dev(A, B, d_and_ptr: int, d_count_a_ptr: int = 0, d_count_b_ptr: int = 0, ctx: "context | None" = None):
+    """asynchronous on the context's stream; device outputs (e.g. torch tensors' data_ptr()): d_and[len(A) * len(B)] row-major,
+    d_count_a[len(A)], d_count_b[len(B)]; a pointer of 0 is not written.  B=None: symmetric."""
+    A = list(A)
+    Bl = None if B is None else list(B)
+    nb = len(A) if Bl is None else len(Bl)
+    ctx = ctx or _list_ctx(A, Bl)
+    if ctx is None:
+        raise ValueError("distance_matrix_dev: every vector is None; pass ctx")
+    check(lib().bmx_distance_matrix_dev(ctx._h, _handles_opt(A), len(A), None if Bl is None else _handles_opt(Bl), nb,
+                                        C.c_void_p(d_and_ptr) if d_and_ptr else None,
+                                        C.c_void_p(d_count_a_ptr) if d_count_a_ptr else None,
+                                        C.c_void_p(d_count_b_ptr) if d_count_b_ptr else None))
 
 
 def _handles(vecs: Sequence[bvector]):
@@ -977,6 +1044,17 @@ class group:
         n = C.c_int()
         check(lib().bmx_group_rccl_ranks(self._h, C.byref(n)))
         return n.value
+
+    def distance_matrix(self, A, B=None, metrics=(COUNT_AND,)) -> np.ndarray:
+        """bmx_gdistance_matrix: distance_matrix over sharded vectors (gbvector lists; None entries are empty)"""
+        A = list(A)
+        Bl = None if B is None else list(B)
+        nb = len(A) if Bl is None else len(Bl)
+        arr, n = _metrics(metrics)
+        out = np.zeros((n, len(A), nb), np.uint64)
+        check(lib().bmx_gdistance_matrix(self._h, _handles_opt(A), len(A), None if Bl is None else _handles_opt(Bl), nb, arr, n,
+                                         _ptr(out) if out.size else None))
+        return out
 
 
 class grs_index:

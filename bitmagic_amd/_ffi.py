@@ -73,6 +73,9 @@ def lib() -> C.CDLL:
         "bmx_pending_free": (i32, [vp, vp]),
         "bmx_count_op2": (i32, [vp, i32, vp, vp, P(u64)]),
         "bmx_count_op2_dev": (i32, [vp, i32, vp, vp, vp]),
+        "bmx_distance": (i32, [vp, vp, vp, P(i32), C.c_size_t, P(u64)]),
+        "bmx_distance_matrix": (i32, [vp, P(vp), C.c_size_t, vp, C.c_size_t, P(i32), C.c_size_t, vp]),
+        "bmx_distance_matrix_dev": (i32, [vp, P(vp), C.c_size_t, vp, C.c_size_t, vp, vp, vp]),
         "bmx_agg_or": (i32, [vp, P(vp), C.c_size_t, P(vp)]),
         "bmx_agg_or_opt": (i32, [vp, P(vp), C.c_size_t, i32, P(vp)]),
         "bmx_agg_and_sub": (i32, [vp, P(vp), C.c_size_t, P(vp), C.c_size_t, P(vp), P(i32)]),
@@ -127,6 +130,7 @@ def lib() -> C.CDLL:
         "bmx_gvec_count": (i32, [vp, vp, P(u64)]),
         "bmx_gvec_count_op2": (i32, [vp, i32, vp, vp, P(u64)]),
         "bmx_gvec_op2": (i32, [vp, i32, vp, vp, i32, P(vp)]),
+        "bmx_gdistance_matrix": (i32, [vp, P(vp), C.c_size_t, vp, C.c_size_t, P(i32), C.c_size_t, vp]),
         "bmx_grs_build": (i32, [vp, vp, P(vp)]),
         "bmx_grs_free": (i32, [vp, vp]),
         "bmx_grs_count": (i32, [vp, P(u64)]),

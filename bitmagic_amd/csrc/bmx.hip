@@ -14,6 +14,7 @@
 #include "bmx_kernels9.h"
 #include "bmx_kernels10.h"
 #include "bmx_kernels11.h"
+#include "bmx_kernels12.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4033,6 +4034,199 @@ int bmx_select_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uin
     dfree(ctx, d);
     if (e != hipSuccess) return fail_hip(e, "bmx_select_batch", __LINE__);
     return rc;
+ABI_END }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------
+// bm::distance_operation (src/bmalgo_impl.h:766) and all-pairs distance matrices (bmx_kernels12.h)
+// ---------------------------------------------------------------------------
+// The device computes |A & B|, |A| and |B|; every metric of bmalgo_impl.h:57-66 follows from them in exact u64 arithmetic.
+static bool dist_metric_ok(int m) { return m >= BMX_COUNT_AND && m <= BMX_COUNT_B; }
+static uint64_t dist_metric(int m, uint64_t ab, uint64_t a, uint64_t b)
+{
+    switch (m) {
+    case BMX_COUNT_AND: return ab;
+    case BMX_COUNT_XOR: return a + b - 2 * ab;
+    case BMX_COUNT_OR: return a + b - ab;
+    case BMX_COUNT_SUB_AB: return a - ab;
+    case BMX_COUNT_SUB_BA: return b - ab;
+    case BMX_COUNT_A: return a;
+    default: return b;
+    }
+}
+static int dist_check_metrics(const int* metrics, size_t nmetrics)
+{
+    if (!metrics || !nmetrics) { g_last_error = "bad argument: metrics must name at least one metric"; return BMX_ERR_BADARG; }
+    for (size_t k = 0; k < nmetrics; ++k)
+        if (!dist_metric_ok(metrics[k])) { g_last_error = "bad argument: metric code outside BMX_COUNT_AND .. BMX_COUNT_B"; return BMX_ERR_BADARG; }
+    return BMX_OK;
+}
+
+// one launch: out[0] = |A & B|, out[1] = |A|, out[2] = |B| (pinned host words: the folding workgroup writes them)
+static int distance_pair_launch(bmx_ctx* ctx, const bmx_vec* a, const bmx_vec* b, u64* out)
+{
+    const uint32_t nblocks = std::max(a->nblocks, b->nblocks);
+    if (!nblocks) { out[0] = out[1] = out[2] = 0; return BMX_OK; }
+    const FoldOut fo{ctx->d_slots, ctx->d_done, out};
+    if (a->nblocks == b->nblocks && a->counts[BMX_BIT] == nblocks && b->counts[BMX_BIT] == nblocks && nblocks >= 2048u) {
+        const u32 total = 256u * 4u * (u32)std::max(ctx->pair_wgs, 1);     // the launch shape of the count_* stream
+        const u32 per_wave = (nblocks + total - 1u) / total;
+        const u32 grid = ((nblocks + per_wave - 1u) / per_wave + 3u) / 4u;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_distance_pair_stream<4, true>), dim3(grid), dim3(256), 0, ctx->stream,
+                           a->d_desc, b->d_desc, nblocks, per_wave, fo);
+    } else {
+        const u32 grid = std::min<u32>((nblocks + 3u) / 4u, 1024u);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_distance_pair_loop<true>), dim3(grid), dim3(256), 0, ctx->stream,
+                           a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, (const u64*)ctx->d_zero, fo);
+    }
+    KCHK();
+    return BMX_OK;
+}
+
+// the device side of a matrix call: operand table, GAP expansion, tile plan, launches.  Everything it allocates is freed
+// before it returns (stream-ordered: the pool hands a block only to work enqueued behind the launches that read it).
+static int distance_matrix_launch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb,
+                                  u64* d_and, u64* d_ca, u64* d_cb)
+{
+    const bool sym = b == nullptr;
+    if (sym) nb = na;
+    int rc = set_dev(ctx); if (rc) return rc;
+    if (d_and && na && nb) HIPCHK(hipMemsetAsync(d_and, 0, na * nb * 8, ctx->stream));
+    if (d_ca && na) HIPCHK(hipMemsetAsync(d_ca, 0, na * 8, ctx->stream));
+    if (d_cb && nb) HIPCHK(hipMemsetAsync(d_cb, 0, nb * 8, ctx->stream));
+    if (!na || !nb) return BMX_OK;
+    const size_t n = na + (sym ? 0 : nb);
+    std::vector<void*> temps;
+    auto cleanup = [&]() { for (void* p : temps) dfree(ctx, p); };
+    // operand table; vectors holding GAP blocks get an expanded copy of their block table (one per distinct vector)
+    std::vector<u64> tab(n + (n + 1) / 2, 0ull);
+    u32* nblk = reinterpret_cast<u32*>(tab.data() + n);
+    std::unordered_map<const bmx_vec*, u64> expanded;
+    uint32_t ncols = 0;
+    for (size_t e = 0; e < n; ++e) {
+        const bmx_vec* v = e < na ? a[e] : b[e - na];
+        if (!v) continue;                                             // an absent vector: empty (build_jaccard_similarity_batch)
+        if (v->ctx != ctx) { cleanup(); g_last_error = "bad argument: an operand belongs to another context"; return BMX_ERR_BADARG; }
+        ncols = std::max(ncols, v->nblocks);
+        nblk[e] = v->nblocks;
+        if (!v->nblocks) continue;
+        if (!v->counts[BMX_GAP]) { tab[e] = (u64)(uintptr_t)v->d_desc; continue; }
+        auto it = expanded.find(v);
+        if (it != expanded.end()) { tab[e] = it->second; continue; }
+        const size_t desc_bytes = ((size_t)v->nblocks * 8 + 255) & ~(size_t)255;
+        const size_t slab_bytes = (size_t)v->counts[BMX_GAP] * 8192;
+        void* buf = nullptr;
+        if ((rc = dmalloc(ctx, &buf, desc_bytes + slab_bytes + 256))) { cleanup(); return rc; }
+        temps.push_back(buf);
+        char* p = (char*)buf;
+        u32* cursor = (u32*)(p + desc_bytes + slab_bytes);
+        if (hipError_t e2 = hipMemsetAsync(cursor, 0, 4, ctx->stream)) { cleanup(); return fail_hip(e2, "hipMemsetAsync", __LINE__); }
+        hipLaunchKernelGGL(k_gap_expand, dim3((v->nblocks + 3u) / 4u), dim3(256), 0, ctx->stream,
+                           v->d_desc, v->nblocks, (u64*)p, (uint4*)(p + desc_bytes), cursor);
+        if (hipError_t e2 = hipGetLastError()) { cleanup(); return fail_hip(e2, "k_gap_expand", __LINE__); }
+        expanded[v] = tab[e] = (u64)(uintptr_t)p;
+    }
+    void* d_tab = nullptr;
+    if ((rc = dmalloc(ctx, &d_tab, tab.size() * 8)) || (rc = h2d_staged(ctx, d_tab, tab.data(), tab.size() * 8))) { dfree(ctx, d_tab); cleanup(); return rc; }
+    temps.push_back(d_tab);
+    const DmTab dt{(const u64*)d_tab, (u32)n, sym ? 0u : (u32)na};
+    if (d_and && ncols) {
+        // tile pairs (ti | tj << 16; symmetric: ti <= tj) x column splits: enough workgroups for two per CU several times
+        // over, a split never longer than 65,535 columns (the u32 counters of the tile kernel)
+        const u32 ta = (u32)((na + DM_T - 1) / DM_T), tb = (u32)((nb + DM_T - 1) / DM_T);
+        std::vector<u32> pairs;
+        for (u32 i = 0; i < ta; ++i)
+            for (u32 j = sym ? i : 0u; j < tb; ++j) pairs.push_back(i | (j << 16));
+        const u32 np = (u32)pairs.size();
+        u32 splits = std::max<u32>(1u, (2048u + np - 1u) / np);
+        splits = std::min(splits, std::max<u32>(1u, ncols / 4u));          // at least 4 columns of work per workgroup
+        splits = std::max(splits, (ncols + 65534u) / 65535u);
+        const u32 cps = (ncols + splits - 1u) / splits;
+        splits = (ncols + cps - 1u) / cps;
+        void* d_pairs = nullptr;
+        if ((rc = dmalloc(ctx, &d_pairs, pairs.size() * 4)) || (rc = h2d_staged(ctx, d_pairs, pairs.data(), pairs.size() * 4))) { dfree(ctx, d_pairs); cleanup(); return rc; }
+        temps.push_back(d_pairs);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_distance_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DM_LDS_BYTES);
+        if (e != hipSuccess) { cleanup(); return fail_hip(e, "hipFuncSetAttribute(k_distance_tile)", __LINE__); }
+        hipLaunchKernelGGL(k_distance_tile, dim3(np, splits), dim3(256), DM_LDS_BYTES, ctx->stream,
+                           dt, (u32)na, (u32)nb, (const u32*)d_pairs, cps, ncols, sym ? 1 : 0, (const u64*)ctx->d_zero, d_and);
+        if ((e = hipGetLastError()) != hipSuccess) { cleanup(); return fail_hip(e, "k_distance_tile", __LINE__); }
+    }
+    if (d_ca || d_cb) {
+        hipError_t e = hipSuccess;
+        const u32 gx = std::max<u32>(1u, std::min<u32>((ncols + 3u) / 4u, 64u));
+        if (sym && d_and && ncols) {
+            hipLaunchKernelGGL(k_distance_diag, dim3((u32)((na + 255) / 256)), dim3(256), 0, ctx->stream, (const u64*)d_and, (u32)na, d_ca, d_cb);
+        } else if (ncols) {
+            if (d_ca) hipLaunchKernelGGL(k_distance_counts, dim3(gx, (u32)na), dim3(256), 0, ctx->stream, dt, 0u, d_ca);
+            if (d_cb) hipLaunchKernelGGL(k_distance_counts, dim3(gx, (u32)nb), dim3(256), 0, ctx->stream, dt, sym ? 0u : (u32)na, d_cb);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) { cleanup(); return fail_hip(e, "k_distance_counts", __LINE__); }
+    }
+    cleanup();
+    return BMX_OK;
+}
+
+// the checks every matrix entry makes before it touches a device
+static int dist_matrix_args(const void* a, size_t na, const void* b, size_t nb)
+{
+    if (na > 65535u || nb > 65535u) { g_last_error = "na, nb <= 65535"; return BMX_ERR_RANGE; }
+    if ((na && !a) || (nb && !b)) { g_last_error = "bad argument: operand list is null"; return BMX_ERR_BADARG; }
+    return BMX_OK;
+}
+
+extern "C" {
+
+int bmx_distance(bmx_ctx* ctx, const bmx_vec* a, const bmx_vec* b, const int* metrics, size_t nmetrics, uint64_t* results)
+{ ABI_TRY
+    int rc = dist_check_metrics(metrics, nmetrics); if (rc) return rc;
+    ARGCHK(results);
+    ARGCHK(ctx && a && b && a->ctx == ctx && b->ctx == ctx);
+    if ((rc = set_dev(ctx))) return rc;
+    if ((rc = distance_pair_launch(ctx, a, b, ctx->h_small))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const u64 ab = ctx->h_small[0], ca = ctx->h_small[1], cb = ctx->h_small[2];
+    for (size_t k = 0; k < nmetrics; ++k) results[k] = dist_metric(metrics[k], ab, ca, cb);
+    return BMX_OK;
+ABI_END }
+
+int bmx_distance_matrix_dev(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb,
+                            uint64_t* d_and, uint64_t* d_count_a, uint64_t* d_count_b)
+{ ABI_TRY
+    int rc = dist_matrix_args(a, na, b, b ? nb : 0); if (rc) return rc;
+    ARGCHK(ctx);
+    return distance_matrix_launch(ctx, a, na, b, nb, (u64*)d_and, (u64*)d_count_a, (u64*)d_count_b);
+ABI_END }
+
+int bmx_distance_matrix(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb,
+                        const int* metrics, size_t nmetrics, uint64_t* out)
+{ ABI_TRY
+    int rc = dist_matrix_args(a, na, b, b ? nb : 0); if (rc) return rc;
+    if ((rc = dist_check_metrics(metrics, nmetrics))) return rc;
+    ARGCHK(out && ctx);
+    if (!b) nb = na;
+    if (!na || !nb) return BMX_OK;
+    if ((rc = set_dev(ctx))) return rc;
+    const size_t nn = na * nb;
+    u64* d = nullptr;
+    if ((rc = dmalloc(ctx, (void**)&d, (nn + na + nb) * 8))) return rc;
+    std::vector<u64> h(nn + na + nb);
+    rc = distance_matrix_launch(ctx, a, na, b, nb, d, d + nn, d + nn + na);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dfree(ctx, d);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail_hip(e, "bmx_distance_matrix", __LINE__);
+    const u64* ca = h.data() + nn;
+    const u64* cb = ca + na;
+    for (size_t k = 0; k < nmetrics; ++k)
+        for (size_t i = 0; i < na; ++i)
+            for (size_t j = 0; j < nb; ++j)
+                out[(k * na + i) * nb + j] = dist_metric(metrics[k], h[i * nb + j], ca[i], cb[j]);
+    return BMX_OK;
 ABI_END }
 
 } // extern "C"

@@ -1020,4 +1020,60 @@ int bmx_gpipeline_describe(bmx_group* g, bmx_gpipeline* p, int member, char* buf
     return bmx_pipeline_describe(g->ctx[(size_t)member], p->pipe[(size_t)member], 0u, 0xFFFFFFFFu, buf, buf_len, n_launches);
 ABI_END }
 
+// bm::distance_operation over every pair of two lists of sharded vectors (src/bmalgo_impl.h:766): block columns are
+// independent, so |a & b|, |a| and |b| are sums over the members; each member runs the single-device matrix over its shards
+// (side by side on the group's workers) and the host adds the members' matrices before it derives the metrics
+int bmx_gdistance_matrix(bmx_group* g, const bmx_gvec* const* a, size_t na, const bmx_gvec* const* b, size_t nb,
+                         const int* metrics, size_t nmetrics, uint64_t* out)
+{ ABI_TRY
+    if (na > 65535u || (b && nb > 65535u)) { bmx_set_last_error("na, nb <= 65535"); return BMX_ERR_RANGE; }
+    ARGCHK(g && (na == 0 || a) && metrics && nmetrics && out);
+    for (size_t k = 0; k < nmetrics; ++k) ARGCHK(metrics[k] >= BMX_COUNT_AND && metrics[k] <= BMX_COUNT_B);
+    const bool sym = b == nullptr;
+    if (sym) nb = na;
+    if (!na || !nb) return BMX_OK;
+    const bmx_gvec* first = nullptr;
+    for (size_t e = 0; e < na + (sym ? 0 : nb); ++e) {
+        const bmx_gvec* v = e < na ? a[e] : b[e - na];
+        if (!v) continue;
+        ARGCHK(v->g == g);
+        if (!first) first = v;
+        else if (v->nblocks != first->nblocks || v->part != first->part) {
+            bmx_set_last_error("sharded operands must cover the same block range (upload them with the same nblocks)"); return BMX_ERR_BADARG;
+        }
+    }
+    const size_t nn = na * nb;
+    std::vector<uint64_t> part((size_t)g->n * 3 * nn, 0);
+    static const int three[3] = {BMX_COUNT_AND, BMX_COUNT_A, BMX_COUNT_B};
+    int rc = for_each_member(g, [&](int m) -> int {
+        std::vector<const bmx_vec*> sa(na, nullptr), sb(sym ? 0 : nb, nullptr);
+        for (size_t i = 0; i < na; ++i) if (a[i]) sa[i] = a[i]->shard[(size_t)m];
+        for (size_t j = 0; j < sb.size(); ++j) if (b[j]) sb[j] = b[j]->shard[(size_t)m];
+        return bmx_distance_matrix(g->ctx[(size_t)m], sa.data(), na, sym ? nullptr : sb.data(), nb, three, 3, part.data() + (size_t)m * 3 * nn);
+    });
+    if (rc) return rc;
+    for (size_t i = 0; i < na; ++i)
+        for (size_t j = 0; j < nb; ++j) {
+            uint64_t ab = 0, ca = 0, cb = 0;
+            for (int m = 0; m < g->n; ++m) {
+                const uint64_t* pm = part.data() + (size_t)m * 3 * nn + i * nb + j;
+                ab += pm[0]; ca += pm[nn]; cb += pm[2 * nn];
+            }
+            for (size_t k = 0; k < nmetrics; ++k) {
+                uint64_t r;
+                switch (metrics[k]) {
+                case BMX_COUNT_AND: r = ab; break;
+                case BMX_COUNT_XOR: r = ca + cb - 2 * ab; break;
+                case BMX_COUNT_OR: r = ca + cb - ab; break;
+                case BMX_COUNT_SUB_AB: r = ca - ab; break;
+                case BMX_COUNT_SUB_BA: r = cb - ab; break;
+                case BMX_COUNT_A: r = ca; break;
+                default: r = cb; break;
+                }
+                out[(k * na + i) * nb + j] = r;
+            }
+        }
+    return BMX_OK;
+ABI_END }
+
 } // extern "C"

@@ -54,6 +54,16 @@ extern "C" {
 #define BMX_XOR 2
 #define BMX_SUB 3
 
+/* metrics of bm::distance_operation: the codes of bm::distance_metric (src/bmalgo_impl.h:57-66, set_operation
+ * src/bmconst.h:175-182) */
+#define BMX_COUNT_AND    6
+#define BMX_COUNT_XOR    7
+#define BMX_COUNT_OR     8
+#define BMX_COUNT_SUB_AB 9
+#define BMX_COUNT_SUB_BA 10
+#define BMX_COUNT_A      11
+#define BMX_COUNT_B      12
+
 /* geometry (src/bmconst.h:55-87) */
 #define BMX_BLOCK_WORDS 2048u
 #define BMX_BLOCK_BITS  65536u
@@ -174,6 +184,18 @@ int bmx_pending_free(bmx_ctx* ctx, bmx_pending* p);
 int bmx_count_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, uint64_t* count);
 /* same, asynchronous on the context's stream; d_count is DEVICE memory (one uint64) */
 int bmx_count_op2_dev(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, uint64_t* d_count);
+/* bm::distance_operation(bv1, bv2, dmit, dmit_end)  src/bmalgo_impl.h:766 -- ONE pass over both operands: one launch folds
+ * |a & b|, |a| and |b|; results[k] = metric k (BMX_COUNT_*; any other code: BMX_ERR_BADARG).  Operands of any block kinds and
+ * lengths (missing blocks are NULL, src/bmalgo_impl.h:785-790); a == b is allowed.  results[k] is SET, not added to. */
+int bmx_distance(bmx_ctx* ctx, const bmx_vec* a, const bmx_vec* b, const int* metrics, size_t nmetrics, uint64_t* results);
+/* all pairs (similarity_batch::calculate, src/bmalgo_similarity.h): out[(k*na + i)*nb + j] = metric k of (a[i], b[j]).
+ * b == NULL: symmetric, B = A (only upper tiles run, mirrored, the diagonal is |a[i]|).  NULL entries in a list are empty
+ * vectors (build_jaccard_similarity_batch skips absent slices).  na, nb <= 65535, else BMX_ERR_RANGE. */
+int bmx_distance_matrix(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb,
+                        const int* metrics, size_t nmetrics, uint64_t* out);
+/* asynchronous on the context's stream, DEVICE outputs: d_and[na*nb], d_count_a[na], d_count_b[nb] (either may be NULL) */
+int bmx_distance_matrix_dev(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb,
+                            uint64_t* d_and, uint64_t* d_count_a, uint64_t* d_count_b);
 
 /* ---- aggregator ---- */
 /* aggregator::combine_or(target, src, n)  src/bmaggregator.h:1101 */
@@ -441,6 +463,10 @@ int bmx_gvec_count(bmx_group* g, const bmx_gvec* a, uint64_t* count);
 int bmx_gvec_count_op2(bmx_group* g, int op, const bmx_gvec* a, const bmx_gvec* b, uint64_t* count);
 /* bvector::bit_and/or/xor/sub (3-operand), result sharded like the operands */
 int bmx_gvec_op2(bmx_group* g, int op, const bmx_gvec* a, const bmx_gvec* b, int opt_compress, bmx_gvec** result);
+/* bmx_distance_matrix over sharded vectors (src/bmalgo_impl.h:766 per pair): every member computes the matrices of its
+ * block range, the per-member |a & b|, |a|, |b| are summed on the host.  Non-null operands must share one cut (same nblocks). */
+int bmx_gdistance_matrix(bmx_group* g, const bmx_gvec* const* a, size_t na, const bmx_gvec* const* b, size_t nb,
+                         const int* metrics, size_t nmetrics, uint64_t* out);
 /* build_rs_index / count_to / select over a sharded vector (src/bm.h:2531,3120,5350): every member indexes its own
  * shard, the shard totals (n x 8 B) are scanned on the host, a query goes to the member that owns its block (rank)
  * or holds the rank-th one (select).  The index refers to `v`: free it before the vector. */

@@ -8,6 +8,8 @@
 //   bm::bvector<>::count / build_rs_index / count_to / rank / select   src/bm.h:2431,2531,3120,1449,5350
 //   bm::bit_import_u32                                                   src/bmbvimport.h:46
 //   bm::count_and/or/xor/sub                                             src/bmalgo.h:49,149,81,115
+//   bm::distance_operation + distance_metric(_descriptor)                src/bmalgo_impl.h:57-66,766
+//   (all pairs in one call: bmx::distance_matrix; similarity batches: bmx/similarity.hpp)
 //   bm::rs_index::count                                                  src/bmrs.h:340
 //   bm::aggregator<BV>::add/reset/combine_or/combine_and/combine_and_sub src/bmaggregator.h:1013-1079
 //   bm::aggregator<BV>::pipeline<agg_opt_only_counts> + combine_and_sub(pipe)  :222-341,1292
@@ -351,6 +353,85 @@ inline size_type count_and(const bvector& a, const bvector& b) { return detail::
 inline size_type count_or(const bvector& a, const bvector& b) { return detail::count_op(BMX_OR, a, b); }     // :149
 inline size_type count_xor(const bvector& a, const bvector& b) { return detail::count_op(BMX_XOR, a, b); }   // :81
 inline size_type count_sub(const bvector& a, const bvector& b) { return detail::count_op(BMX_SUB, a, b); }   // :115
+
+/// bm::distance_metric (src/bmalgo_impl.h:57-66): the set_operation codes of the count metrics
+enum distance_metric {
+    COUNT_AND = BMX_COUNT_AND, COUNT_XOR = BMX_COUNT_XOR, COUNT_OR = BMX_COUNT_OR, COUNT_SUB_AB = BMX_COUNT_SUB_AB,
+    COUNT_SUB_BA = BMX_COUNT_SUB_BA, COUNT_A = BMX_COUNT_A, COUNT_B = BMX_COUNT_B
+};
+
+/// bm::distance_metric_descriptor: a metric code and the result it accumulates (64-bit: BM64ADDR's size_type)
+struct distance_metric_descriptor {
+    typedef bmx::size_type size_type;
+    distance_metric metric;
+    size_type result;
+    distance_metric_descriptor(distance_metric m) noexcept : metric(m), result(0) {}
+    distance_metric_descriptor() noexcept : metric(COUNT_XOR), result(0) {}
+    void reset() noexcept { result = 0; }
+};
+
+namespace detail {
+// every metric from |a & b|, |a|, |b| (exact in u64)
+inline size_type metric_value(distance_metric m, size_type ab, size_type a, size_type b)
+{
+    switch (m) {
+    case COUNT_AND: return ab;
+    case COUNT_XOR: return a + b - 2 * ab;
+    case COUNT_OR: return a + b - ab;
+    case COUNT_SUB_AB: return a - ab;
+    case COUNT_SUB_BA: return b - ab;
+    case COUNT_A: return a;
+    default: return b;
+    }
+}
+inline const bmx_vec* handle_or_null(const bvector* v) { return (v && !v->empty_handle()) ? v->handle() : nullptr; }
+} // namespace detail
+
+/// bm::distance_operation (src/bmalgo_impl.h:766): every metric of [dmit, dmit_end) of the pair (bv1, bv2) in ONE pass over
+/// both vectors; the values are ADDED to the descriptors' results (so that calls can accumulate, as the reference documents)
+inline void distance_operation(const bvector& bv1, const bvector& bv2, distance_metric_descriptor* dmit, distance_metric_descriptor* dmit_end)
+{
+    if (dmit == dmit_end) return;
+    size_type ab = 0, ca = 0, cb = 0;
+    if (!bv1.empty_handle() && !bv2.empty_handle()) {
+        const int three[3] = {BMX_COUNT_AND, BMX_COUNT_A, BMX_COUNT_B};
+        uint64_t r[3] = {0, 0, 0};
+        check(bmx_distance(bv1.get_context().handle(), bv1.handle(), bv2.handle(), three, 3, r));
+        ab = r[0]; ca = r[1]; cb = r[2];
+    } else {
+        ca = bv1.empty_handle() ? 0 : bv1.count();
+        cb = bv2.empty_handle() ? 0 : bv2.count();
+    }
+    for (; dmit != dmit_end; ++dmit) dmit->result += detail::metric_value(dmit->metric, ab, ca, cb);
+}
+
+/// all pairs in one device call: out[(k * a.size() + i) * b.size() + j] = metric k of (*a[i], *b[j]); null pointers (and
+/// vectors never filled) are empty vectors.  The vectors must share one context.
+inline std::vector<uint64_t> distance_matrix(const std::vector<const bvector*>& a, const std::vector<const bvector*>& b,
+                                             const std::vector<distance_metric>& metrics)
+{
+    std::vector<uint64_t> out(metrics.size() * a.size() * b.size(), 0);
+    std::vector<const bmx_vec*> ha(a.size()), hb(b.size());
+    bmx_ctx* ctx = nullptr;
+    for (size_t i = 0; i < a.size(); ++i) { ha[i] = detail::handle_or_null(a[i]); if (ha[i] && !ctx) ctx = a[i]->get_context().handle(); }
+    for (size_t j = 0; j < b.size(); ++j) { hb[j] = detail::handle_or_null(b[j]); if (hb[j] && !ctx) ctx = b[j]->get_context().handle(); }
+    if (!ctx || out.empty()) return out;                           // no vector holds anything: every metric is 0
+    std::vector<int> m(metrics.begin(), metrics.end());
+    check(bmx_distance_matrix(ctx, ha.data(), ha.size(), hb.data(), hb.size(), m.data(), m.size(), out.data()));
+    return out;
+}
+/// the symmetric form (B = A): only the upper tiles are computed on the device
+inline std::vector<uint64_t> distance_matrix(const std::vector<const bvector*>& a, const std::vector<distance_metric>& metrics)
+{
+    std::vector<uint64_t> out(metrics.size() * a.size() * a.size(), 0);
+    std::vector<const bmx_vec*> ha(a.size());
+    bmx_ctx* ctx = nullptr;
+    for (size_t i = 0; i < a.size(); ++i) { ha[i] = detail::handle_or_null(a[i]); if (ha[i] && !ctx) ctx = a[i]->get_context().handle(); }
+    if (!ctx || out.empty()) return out;
+    std::vector<int> m(metrics.begin(), metrics.end());
+    check(bmx_distance_matrix(ctx, ha.data(), ha.size(), nullptr, 0, m.data(), m.size(), out.data()));
+    return out;
+}
 
 /// run options (src/bmaggregator.h:62-103)
 template <bool OBvects = true, bool OCounts = false, bool OSearchMasks = false>

@@ -186,6 +186,22 @@ inline size_type count_or(const gbvector& a, const gbvector& b) { return detail:
 inline size_type count_xor(const gbvector& a, const gbvector& b) { return detail::gcount_op(BMX_XOR, a, b); }
 inline size_type count_sub(const gbvector& a, const gbvector& b) { return detail::gcount_op(BMX_SUB, a, b); }
 
+/// distance_matrix over sharded vectors (bmx_gdistance_matrix): the members' |a & b|, |a|, |b| are summed on the host.
+/// b empty and `symmetric`: B = A.  Null pointers and never-filled vectors are empty.
+inline std::vector<uint64_t> distance_matrix(device_group& g, const std::vector<const gbvector*>& a, const std::vector<const gbvector*>& b,
+                                             const std::vector<distance_metric>& metrics, bool symmetric = false)
+{
+    const size_t nb = symmetric ? a.size() : b.size();
+    std::vector<uint64_t> out(metrics.size() * a.size() * nb, 0);
+    if (out.empty()) return out;
+    std::vector<const bmx_gvec*> ha(a.size()), hb(b.size());
+    for (size_t i = 0; i < a.size(); ++i) ha[i] = (a[i] && !a[i]->empty_handle()) ? a[i]->handle() : nullptr;
+    for (size_t j = 0; j < b.size(); ++j) hb[j] = (b[j] && !b[j]->empty_handle()) ? b[j]->handle() : nullptr;
+    std::vector<int> m(metrics.begin(), metrics.end());
+    check(bmx_gdistance_matrix(g.handle(), ha.data(), ha.size(), symmetric ? nullptr : hb.data(), nb, m.data(), m.size(), out.data()));
+    return out;
+}
+
 /// bmx_gcollection_prepare: every member of the group transposes its block range of the vectors into a packed collection
 /// (role BMX_ROLE_OR / BMX_ROLE_AND / BMX_ROLE_SUB); the group's aggregations and pipelines over those vectors then use it
 inline void collection_prepare(device_group& g, const std::vector<const gbvector*>& vecs, int role)
