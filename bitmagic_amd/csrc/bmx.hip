@@ -53,12 +53,13 @@ int bmx_abi_caught(int kind, const char* what)
     try { g_last_error = std::string("unexpected C++ exception inside the library: ") + (what ? what : "(not a std::exception)"); } catch (...) {}
     return BMX_ERR_DEVICE;
 }
-// debug fault injection (bmx_debug_inject_failure): the ABI entry `after` calls from now on this thread throws
+// debug fault injection (bmx_debug_inject_failure): the outermost ABI entry `after` such entries from now on this thread throws
 static thread_local int g_inject_kind = 0;
 static thread_local long long g_inject_after = -1;
+thread_local int bmx_abi_depth = 0;
 void bmx_abi_enter()
 {
-    if (g_inject_after < 0) return;
+    if (bmx_abi_depth != 1 || g_inject_after < 0) return;
     if (g_inject_after-- > 0) return;
     const int k = g_inject_kind; g_inject_kind = 0;
     if (k == 1) throw std::bad_alloc();
@@ -71,6 +72,14 @@ static int vec_build_tdir(bmx_ctx* ctx, bmx_vec* v);
 static void coll_drop_vector(bmx_ctx* ctx, uint64_t uid);
 static bool coll_evict_one(bmx_ctx* ctx);
 static int set_dev(const bmx_ctx* ctx) { HIPCHK(hipSetDevice(ctx->device)); return BMX_OK; }
+
+// debug fault injection (bmx_debug_inject_failure kinds 4 and 6): this device allocation fails, or throws std::bad_alloc
+static int dmalloc_injected(bmx_ctx* ctx)
+{
+    if (ctx->fail_dmalloc_after < 0 || ctx->fail_dmalloc_after-- != 0) return BMX_OK;
+    if (ctx->fail_dmalloc_throws) throw std::bad_alloc();
+    g_last_error = "injected device allocation failure"; return BMX_ERR_BADALLOC;
+}
 
 static size_t pool_round(size_t bytes)
 {
@@ -162,9 +171,7 @@ static int dmalloc_at(bmx_ctx* ctx, void** p, size_t bytes, int line)
 static int dmalloc_(bmx_ctx* ctx, void** p, size_t bytes, int line)
 {
     *p = nullptr;
-    if (ctx->fail_dmalloc_after >= 0 && ctx->fail_dmalloc_after-- == 0) {      // debug fault injection
-        g_last_error = "injected device allocation failure"; return BMX_ERR_BADALLOC;
-    }
+    if (int rc = dmalloc_injected(ctx)) return rc;
     size_t sz = pool_round(ctx->redzone ? rz_user_end(bytes) + 2u * RZ_BYTES : bytes);
     auto it = ctx->pool_free.lower_bound(sz);
     if (it != ctx->pool_free.end() && it->first <= sz + sz / 4) {          // best fit within 25 % slack
@@ -229,7 +236,7 @@ static int ensure_at(bmx_ctx* ctx, void** buf, size_t* cur, size_t need, int lin
 {
     if (*cur >= need) return BMX_OK;
     ensure_release(ctx, buf, cur);
-    if (ctx->fail_dmalloc_after >= 0 && ctx->fail_dmalloc_after-- == 0) { g_last_error = "injected device allocation failure"; return BMX_ERR_BADALLOC; }
+    if (int rc = dmalloc_injected(ctx)) return rc;
     if (ctx->redzone) {
         const size_t block = rz_user_end(need) + 2u * RZ_BYTES;
         void* raw = nullptr;
@@ -242,26 +249,42 @@ static int ensure_at(bmx_ctx* ctx, void** buf, size_t* cur, size_t need, int lin
 }
 #define ensure(ctx, buf, cur, need) ensure_at((ctx), (buf), (cur), (need), __LINE__)
 
+// a temporary device block, move-only (dmalloc(ctx, &b.p, bytes) keeps the line of the allocation): given back when the scope
+// ends, or earlier through reset()
+struct DevBuf {
+    bmx_ctx* ctx; void* p = nullptr;
+    explicit DevBuf(bmx_ctx* c) : ctx(c) {}
+    DevBuf(DevBuf&& o) noexcept : ctx(o.ctx), p(o.p) { o.p = nullptr; }     // (declaring it deletes the copies)
+    ~DevBuf() { try { reset(); } catch (...) {} }          // (see Releaser, bmx_internal.h)
+    void reset() { dfree(ctx, p); p = nullptr; }
+    void* release() { void* q = p; p = nullptr; return q; }
+    template <class T> explicit operator T*() const { return (T*)p; }
+};
+
 // ---------------------------------------------------------------------------
 // column-major packed GAP collections (bmx_kernels6.h, member directory bmx_kernels8.h)
 // ---------------------------------------------------------------------------
+// the only place a collection's members are freed: coll_free for one in ctx->colls, the owner of coll_build for one being built
+static void coll_release(bmx_ctx* ctx, bmx_coll* c)
+{
+    dfree(ctx, c->d_runs); dfree(ctx, c->d_off); dfree(ctx, c->d_cnt); dfree(ctx, c->d_flags); dfree(ctx, c->d_cnt_s);
+    dfree(ctx, c->d_dir); dfree(ctx, c->d_dir_s); dfree(ctx, c->d_bt);
+    delete c;
+}
 static void coll_free(bmx_ctx* ctx, size_t idx)
 {
     bmx_coll* c = ctx->colls[idx];
-    dfree(ctx, c->d_runs); dfree(ctx, c->d_off); dfree(ctx, c->d_cnt); dfree(ctx, c->d_flags); dfree(ctx, c->d_cnt_s);
-    dfree(ctx, c->d_dir); dfree(ctx, c->d_dir_s); dfree(ctx, c->d_bt);
     ctx->pack_bytes -= std::min<uint64_t>(ctx->pack_bytes, c->bytes);
     ctx->colls.erase(ctx->colls.begin() + (long)idx);
     ++ctx->coll_gen;                                       // pipelines that resolved their groups against a collection look again
-    delete c->index;
-    delete c;
+    coll_release(ctx, c);
 }
 
 // a vector is going away (the caller has synchronised the stream): every collection that holds its runs goes with it
 static void coll_drop_vector(bmx_ctx* ctx, uint64_t uid)
 {
     for (size_t i = ctx->colls.size(); i-- > 0;)
-        if (ctx->colls[i]->index->count(uid)) coll_free(ctx, i);
+        if (ctx->colls[i]->index.count(uid)) coll_free(ctx, i);
 }
 
 // device memory is short: the least recently used collection goes (the caller retries its allocation); false = none left
@@ -310,18 +333,18 @@ static bmx_coll* coll_cover(bmx_ctx* ctx, const uint64_t* uids, size_t n, int po
     std::vector<u32> idx(n);
     for (bmx_coll* c : ctx->colls) {
         if (c->polarity != polarity || !n || c->has_bit) continue;
-        if (!c->index->count(uids[0])) continue;
+        if (!c->index.count(uids[0])) continue;
         bool all = true;
         for (size_t i = 0; i < n && all; ++i) {
-            auto it = c->index->find(uids[i]);
-            if (it == c->index->end()) all = false; else idx[i] = it->second;
+            auto it = c->index.find(uids[i]);
+            if (it == c->index.end()) all = false; else idx[i] = it->second;
         }
         if (!all) continue;
         bool f = false;
-        if (n >= c->index->size()) {                       // names every distinct member?
+        if (n >= c->index.size()) {                        // names every distinct member?
             std::vector<u8> seen(c->nvec, 0); size_t distinct = 0;
             for (size_t i = 0; i < n; ++i) if (!seen[idx[i]]) { seen[idx[i]] = 1; ++distinct; }
-            f = distinct == c->index->size();
+            f = distinct == c->index.size();
         }
         if (!best || (f && !best_full) || (f == best_full && c->nvec < best->nvec)) {
             best = c; best_full = f;
@@ -338,24 +361,21 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
     *out = nullptr;
     int rc;
     uint32_t ncols = 0; uint64_t alg = 0;
-    std::vector<const u64*> descs(n); std::vector<uint32_t> nblk(n);
+    std::vector<const u64*> descs(n); std::vector<uint32_t> nblk(n); std::vector<u64> tab;      // (host tables of the passes)
     for (size_t i = 0; i < n; ++i) {
         descs[i] = v[i]->d_desc; nblk[i] = v[i]->nblocks; ncols = std::max(ncols, v[i]->nblocks);
         alg += 2ull * v[i]->gap_words;                    // (device slabs pad blocks to 16 B: an upper bound, refined below)
     }
     if (!ncols || (ncols + 3u) / 4u > 65535u) return BMX_OK;        // (grid.y of the scatter pass; longer vectors keep the table kernels)
-    bmx_coll* c = new (std::nothrow) bmx_coll();
-    if (!c) return BMX_ERR_BADALLOC;
-    c->polarity = polarity; c->ncols = ncols; c->nvec = (uint32_t)n;
-    c->d_runs = nullptr; c->d_off = nullptr; c->d_cnt = nullptr; c->d_flags = nullptr; c->d_cnt_s = nullptr; c->d_dir = nullptr; c->d_dir_s = nullptr;
-    c->entries = 0; c->bytes = 0; c->has_bit = false; c->build_ms = 0.f; c->alg_bytes = alg; c->prepared = false;
+    // an error path: the temporaries below go first (dfree is stream-ordered), then the deleter waits for the stream -- the host
+    // tables above are still alive then -- and frees the collection
+    struct CollDrop { bmx_ctx* ctx; void operator()(bmx_coll* c) const { try { (void)hipStreamSynchronize(ctx->stream); coll_release(ctx, c); } catch (...) {} } };
+    std::unique_ptr<bmx_coll, CollDrop> c(new bmx_coll(), CollDrop{ctx});
+    c->polarity = polarity; c->ncols = ncols; c->nvec = (uint32_t)n; c->alg_bytes = alg;
     c->key.resize(n);
-    c->index = new (std::nothrow) std::unordered_map<uint64_t, uint32_t>();
-    if (!c->index) { delete c; return BMX_ERR_BADALLOC; }
-    for (size_t i = 0; i < n; ++i) { c->key[i] = v[i]->uid; c->index->emplace(v[i]->uid, (uint32_t)i); }      // (a repeated vector keeps its first index)
+    for (size_t i = 0; i < n; ++i) { c->key[i] = v[i]->uid; c->index.emplace(v[i]->uid, (uint32_t)i); }      // (a repeated vector keeps its first index)
     struct BuildGuard { bmx_ctx* c; BuildGuard(bmx_ctx* x) : c(x) { ++c->coll_building; } ~BuildGuard() { --c->coll_building; } } guard(ctx);   // (no eviction from under a build)
-    void* d_descs = nullptr; void* d_nblk = nullptr; u32* d_pre = nullptr; u32* d_sgl = nullptr; u32* d_words = nullptr;
-    void* d_optab = nullptr; u32* d_bt = nullptr;
+    DevBuf d_descs(ctx), d_nblk(ctx), d_pre(ctx), d_sgl(ctx), d_words(ctx), d_optab(ctx), d_bt(ctx);
     const bool split = polarity == 1 && ctx->coll_split != 0;
     // sparse operands, OR / SUB role: the tile build (bmx_kernels10.h).  coll_build: -1 = where the operands average <= 4.1
     // 16-byte chunks per GAP block (the rows of 14 columns fit one wave load nearly always), 0 = never, 1 = whenever possible
@@ -368,40 +388,30 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
     u64 total = 0;
     const size_t dir_bytes = ((size_t)n + 1) * ncols * 4;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto fail = [&](int code) {
-        (void)hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_descs); dfree(ctx, d_nblk); dfree(ctx, d_pre); dfree(ctx, d_sgl); dfree(ctx, d_words); dfree(ctx, d_optab); dfree(ctx, d_bt);
-        dfree(ctx, c->d_runs); dfree(ctx, c->d_off); dfree(ctx, c->d_cnt); dfree(ctx, c->d_flags); dfree(ctx, c->d_cnt_s);
-        dfree(ctx, c->d_dir); dfree(ctx, c->d_dir_s);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        delete c->index;
-        delete c;
-        return code;
-    };
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{e0, e1};
     if (tiles) {
         // ---- the tile build: two passes over the run lists, a workgroup per tile of 14 columns (bmx_kernels10.h) ----
         const u32 ntiles = (ncols + ORR_TILE - 1u) / ORR_TILE, ngroups = ((u32)n + C2_GROUP - 1u) / C2_GROUP;
-        std::vector<u64> tab(n * 4, 0ull);
+        tab.assign(n * 4, 0ull);
         for (size_t i = 0; i < n; ++i) {
             const bmx_vec* o = v[i];
-            if (!o->d_tdir && (rc = vec_build_tdir(ctx, const_cast<bmx_vec*>(o)))) return fail(rc);      // (a cache of the immutable vector's layout)
+            if (!o->d_tdir && (rc = vec_build_tdir(ctx, const_cast<bmx_vec*>(o)))) return rc;      // (a cache of the immutable vector's layout)
             tab[i * 4] = (u64)(uintptr_t)o->d_tdir; tab[i * 4 + 1] = (u64)(uintptr_t)o->d_gaps;
             tab[i * 4 + 2] = (u64)(uintptr_t)o->d_desc; tab[i * 4 + 3] = (u64)o->nblocks;
         }
-        if ((rc = dmalloc(ctx, &d_optab, std::max<size_t>(tab.size() * 8, 64))) ||
-            (rc = dmalloc(ctx, (void**)&d_bt, (size_t)ntiles * ngroups * 16 * 4)) || (rc = dmalloc(ctx, (void**)&d_words, (size_t)ncols * 4)) ||
+        if ((rc = dmalloc(ctx, &d_optab.p, std::max<size_t>(tab.size() * 8, 64))) ||
+            (rc = dmalloc(ctx, &d_bt.p, (size_t)ntiles * ngroups * 16 * 4)) || (rc = dmalloc(ctx, &d_words.p, (size_t)ncols * 4)) ||
             (rc = dmalloc(ctx, (void**)&c->d_off, ((size_t)ncols + 1) * 8)) || (rc = dmalloc(ctx, (void**)&c->d_cnt, (size_t)ncols * 4)) ||
-            (rc = dmalloc(ctx, (void**)&c->d_flags, (size_t)ncols * 4)) || (rc = dmalloc(ctx, (void**)&c->d_cnt_s, (size_t)ncols * 4))) return fail(rc);
+            (rc = dmalloc(ctx, (void**)&c->d_flags, (size_t)ncols * 4)) || (rc = dmalloc(ctx, (void**)&c->d_cnt_s, (size_t)ncols * 4))) return rc;
         // (the member directory -- 8 B per member and column, 2 GB for configs[4] -- is built by coll_ensure_dir when a call that
         // names only some of the members first needs it: a list of all members streams the column regions without it)
         hipError_t e = hipEventCreate(&e0);
         if (e == hipSuccess) e = hipEventCreate(&e1);
         if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_optab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return fail(fail_hip(e, "coll_build (tiles)", __LINE__));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_optab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return fail_hip(e, "coll_build (tiles)", __LINE__);
         hipLaunchKernelGGL(k_coll2_count, dim3(ntiles), dim3(1024), 0, ctx->stream, (const u32x4*)d_optab, (u32)n, ncols, ngroups, ctx->xcd_swz,
-                           C2CountOut{c->d_cnt, c->d_cnt_s, c->d_flags, d_words, d_bt});
+                           C2CountOut{c->d_cnt, c->d_cnt_s, c->d_flags, (u32*)d_words, (u32*)d_bt});
         hipLaunchKernelGGL(k_coll_offsets, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_words, ncols, c->d_off);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&total, c->d_off + ncols, 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -409,13 +419,13 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (the operand table came from pageable memory: done too)
         float ms_count = 0.f;
         if (e == hipSuccess) e = hipEventElapsedTime(&ms_count, e0, e1);
-        if (e != hipSuccess) return fail(fail_hip(e, "coll_build (tile count)", __LINE__));
+        if (e != hipSuccess) return fail_hip(e, "coll_build (tile count)", __LINE__);
         c->entries = total;
         // (build_ms is the device time of the two passes: the allocation between them -- gigabytes the driver may have to map and
         // clear, 0.1 to 120 ms on the boxes of this pool -- is host time the caller sees in the call's wall time)
-        if ((rc = dmalloc(ctx, (void**)&c->d_runs, std::max<size_t>((size_t)total * 4, 64)))) return fail(rc);
+        if ((rc = dmalloc(ctx, (void**)&c->d_runs, std::max<size_t>((size_t)total * 4, 64)))) return rc;
         e = hipEventRecord(e0, ctx->stream);
-        if (e != hipSuccess) return fail(fail_hip(e, "coll_build (tile scatter)", __LINE__));
+        if (e != hipSuccess) return fail_hip(e, "coll_build (tile scatter)", __LINE__);
         const size_t lds = (size_t)ngroups * 16 * 4 * 2;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_coll2_scatter<8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess) {
@@ -426,16 +436,16 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
         if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
         if (e == hipSuccess) e = hipEventSynchronize(e1);
         if (e == hipSuccess) e = hipEventElapsedTime(&c->build_ms, e0, e1);
-        if (e != hipSuccess) return fail(fail_hip(e, "coll_build (tile scatter)", __LINE__));
+        if (e != hipSuccess) return fail_hip(e, "coll_build (tile scatter)", __LINE__);
         c->build_ms += ms_count;
-        c->d_bt = d_bt; d_bt = nullptr; c->dir_pending = true;
+        c->d_bt = (u32*)d_bt.release(); c->dir_pending = true;
     } else {
-    if ((rc = dmalloc(ctx, &d_descs, n * 8)) || (rc = dmalloc(ctx, &d_nblk, n * 4)) ||
-        (rc = dmalloc(ctx, (void**)&d_pre, (size_t)n * ncols * 4)) ||
+    if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4)) ||
+        (rc = dmalloc(ctx, &d_pre.p, (size_t)n * ncols * 4)) ||
         (rc = dmalloc(ctx, (void**)&c->d_off, ((size_t)ncols + 1) * 8)) || (rc = dmalloc(ctx, (void**)&c->d_cnt, (size_t)ncols * 4)) ||
-        (rc = dmalloc(ctx, (void**)&c->d_flags, (size_t)ncols * 4))) return fail(rc);
-    if (split && ((rc = dmalloc(ctx, (void**)&d_sgl, (size_t)n * ncols * 4)) || (rc = dmalloc(ctx, (void**)&d_words, (size_t)ncols * 4)) ||
-                  (rc = dmalloc(ctx, (void**)&c->d_cnt_s, (size_t)ncols * 4)))) return fail(rc);
+        (rc = dmalloc(ctx, (void**)&c->d_flags, (size_t)ncols * 4))) return rc;
+    if (split && ((rc = dmalloc(ctx, &d_sgl.p, (size_t)n * ncols * 4)) || (rc = dmalloc(ctx, &d_words.p, (size_t)ncols * 4)) ||
+                  (rc = dmalloc(ctx, (void**)&c->d_cnt_s, (size_t)ncols * 4)))) return rc;
     // lanes per block in the passes that walk run lists: by the average block length
     uint64_t nblocks_gap = 0, gap_words_all = 0;
     for (size_t i = 0; i < n; ++i) { nblocks_gap += v[i]->counts[BMX_GAP]; gap_words_all += v[i]->gap_words; }
@@ -443,19 +453,19 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_descs, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return fail(fail_hip(e, "coll_build", __LINE__));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return fail_hip(e, "coll_build", __LINE__);
     hipLaunchKernelGGL(k_coll_count, dim3((ncols + 255) / 256), dim3(256), 0, ctx->stream, (const u64* const*)d_descs,
-                       (const u32*)d_nblk, (u32)n, ncols, (u32)polarity, d_pre, c->d_cnt, c->d_flags);
+                       (const u32*)d_nblk, (u32)n, ncols, (u32)polarity, (u32*)d_pre, c->d_cnt, c->d_flags);
     if (split) {
         // single-bit runs per (operand, column) -> their prefix per column -> the column's size in 32-bit words
         if (short_blocks) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coll_count_singles<8>), dim3((u32)n, ((ncols + 31) / 32 + COLL_YT - 1) / COLL_YT), dim3(256), 0, ctx->stream,
-                                             (const u64* const*)d_descs, (const u32*)d_nblk, ncols, d_sgl);
+                                             (const u64* const*)d_descs, (const u32*)d_nblk, ncols, (u32*)d_sgl);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coll_count_singles<64>), dim3((u32)n, ((ncols + 3) / 4 + COLL_YT - 1) / COLL_YT), dim3(256), 0, ctx->stream,
-                                (const u64* const*)d_descs, (const u32*)d_nblk, ncols, d_sgl);
-        hipLaunchKernelGGL(k_coll_prefix_singles, dim3((ncols + 255) / 256), dim3(256), 0, ctx->stream, d_sgl, (u32)n, ncols,
-                           (const u32*)c->d_cnt, c->d_cnt_s, d_words);
+                                (const u64* const*)d_descs, (const u32*)d_nblk, ncols, (u32*)d_sgl);
+        hipLaunchKernelGGL(k_coll_prefix_singles, dim3((ncols + 255) / 256), dim3(256), 0, ctx->stream, (u32*)d_sgl, (u32)n, ncols,
+                           (const u32*)c->d_cnt, c->d_cnt_s, (u32*)d_words);
         hipLaunchKernelGGL(k_coll_offsets, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_words, ncols, c->d_off);
     } else
     hipLaunchKernelGGL(k_coll_offsets, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)c->d_cnt, ncols, c->d_off);
@@ -465,14 +475,14 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (descs / nblk are read from pageable memory: they are done too)
     float ms_count = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms_count, e0, e1);
-    if (e != hipSuccess) return fail(fail_hip(e, "coll_build (count)", __LINE__));
+    if (e != hipSuccess) return fail_hip(e, "coll_build (count)", __LINE__);
     c->entries = total;
     // (build_ms = device time of the passes: the allocations between them are host time, see the tile build above)
     const size_t dir_b = ((size_t)n + 1) * ncols * 4;
     if ((rc = dmalloc(ctx, (void**)&c->d_runs, std::max<size_t>((size_t)total * 4, 64))) ||
-        (rc = dmalloc(ctx, (void**)&c->d_dir, dir_b)) || (split && (rc = dmalloc(ctx, (void**)&c->d_dir_s, dir_b)))) return fail(rc);
+        (rc = dmalloc(ctx, (void**)&c->d_dir, dir_b)) || (split && (rc = dmalloc(ctx, (void**)&c->d_dir_s, dir_b)))) return rc;
     e = hipEventRecord(e0, ctx->stream);
-    if (e != hipSuccess) return fail(fail_hip(e, "coll_build (scatter)", __LINE__));
+    if (e != hipSuccess) return fail_hip(e, "coll_build (scatter)", __LINE__);
     if (total && split) {
         if (short_blocks) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coll_scatter_split<8>), dim3((u32)n, ((ncols + 31) / 32 + COLL_YT - 1) / COLL_YT), dim3(256), 0, ctx->stream,
                                              (const u64* const*)d_descs, (const u32*)d_nblk, ncols, (const u32*)d_pre, (const u32*)d_sgl,
@@ -497,11 +507,10 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
     if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
     if (e == hipSuccess) e = hipEventSynchronize(e1);
     if (e == hipSuccess) e = hipEventElapsedTime(&c->build_ms, e0, e1);
-    if (e != hipSuccess) return fail(fail_hip(e, "coll_build (scatter)", __LINE__));
+    if (e != hipSuccess) return fail_hip(e, "coll_build (scatter)", __LINE__);
     c->build_ms += ms_count;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    dfree(ctx, d_descs); dfree(ctx, d_nblk); dfree(ctx, d_pre); dfree(ctx, d_sgl); dfree(ctx, d_words); dfree(ctx, d_optab); dfree(ctx, d_bt);
+    d_descs.reset(); d_nblk.reset(); d_pre.reset(); d_sgl.reset(); d_words.reset(); d_optab.reset(); d_bt.reset();
     c->bytes = (uint64_t)total * 4 + (uint64_t)ncols * (split ? 20 : 16) + 8 + (c->dir_pending ? (uint64_t)((ncols + ORR_TILE - 1u) / ORR_TILE) * ((n + C2_GROUP - 1) / C2_GROUP) * 64 : (uint64_t)dir_bytes * (split ? 2 : 1));
     c->run_bytes = (uint64_t)total * 4;
     c->id = ++ctx->coll_next_id;
@@ -515,10 +524,10 @@ static int coll_build(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int polar
         if (lru == ctx->colls.size()) break;
         coll_free(ctx, lru);
     }
-    ctx->colls.push_back(c);
+    ctx->colls.push_back(c.get());
     ctx->pack_bytes += c->bytes;
     ++ctx->coll_gen;
-    *out = c;
+    *out = c.release();
     return BMX_OK;
 }
 
@@ -538,7 +547,7 @@ static int coll_resolve(bmx_ctx* ctx, const bmx_vec* const* v, size_t n, int pol
     for (size_t i = 0; i < n; ++i) need += 2ull * v[i]->gap_words;
     if (need > ctx->pack_cap) return BMX_OK;
     int rc = coll_build(ctx, v, n, polarity, out, keep);
-    if (!rc && *out) { *full = true; if (members) { members->resize(n); for (size_t i = 0; i < n; ++i) (*members)[i] = (*(*out)->index)[uids[i]]; } }
+    if (!rc && *out) { *full = true; if (members) { members->resize(n); for (size_t i = 0; i < n; ++i) (*members)[i] = (*out)->index[uids[i]]; } }
     return rc;
 }
 
@@ -631,7 +640,7 @@ static int coll_ensure_dir(bmx_ctx* ctx, bmx_coll* c)
         tab[i * 4 + 2] = (u64)(uintptr_t)o->d_desc; tab[i * 4 + 3] = (u64)o->nblocks;
     }
     const size_t dir_bytes = (n + 1) * (size_t)ncols * 4;
-    void* d_optab = nullptr;
+    DevBuf d_optab(ctx), dir(ctx), dir_s(ctx);
     CollPin pin; pin.pin(c);                                                  // (the allocations below must not evict it)
     // the directory counts against the packing budget like the runs do: least recently used, unpinned collections make room first
     while (ctx->pack_bytes + 2ull * dir_bytes > ctx->pack_cap) {
@@ -642,21 +651,20 @@ static int coll_ensure_dir(bmx_ctx* ctx, bmx_coll* c)
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) break;              // (nothing may still read it)
         coll_free(ctx, lru);
     }
-    if ((rc = dmalloc(ctx, &d_optab, std::max<size_t>(tab.size() * 8, 64))) || (rc = dmalloc(ctx, (void**)&c->d_dir, dir_bytes)) ||
-        (rc = dmalloc(ctx, (void**)&c->d_dir_s, dir_bytes))) {
-        dfree(ctx, d_optab); dfree(ctx, c->d_dir); dfree(ctx, c->d_dir_s); c->d_dir = c->d_dir_s = nullptr; return rc;
-    }
-    hipError_t e = hipMemcpyAsync(d_optab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+    if ((rc = dmalloc(ctx, &d_optab.p, std::max<size_t>(tab.size() * 8, 64))) || (rc = dmalloc(ctx, &dir.p, dir_bytes)) ||
+        (rc = dmalloc(ctx, &dir_s.p, dir_bytes))) return rc;
+    hipError_t e = hipMemcpyAsync(d_optab.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream);
     const size_t lds = (size_t)ngroups * 16 * 4 * 2;
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_coll2_scatter<8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_coll2_scatter<8, 4>), dim3(ntiles), dim3(256), lds, ctx->stream, (const u32x4*)d_optab, (u32)n, ncols, ngroups, ctx->xcd_swz,
-                           (const u32*)c->d_bt, (const u64*)c->d_off, (const u32*)c->d_cnt, (const u32*)c->d_cnt_s, c->d_runs, c->d_dir, c->d_dir_s, C2_SKIP_RUNS);
+                           (const u32*)c->d_bt, (const u64*)c->d_off, (const u32*)c->d_cnt, (const u32*)c->d_cnt_s, c->d_runs, (u32*)dir, (u32*)dir_s, C2_SKIP_RUNS);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);                // (the table came from pageable memory)
-    dfree(ctx, d_optab);
-    if (e != hipSuccess) { dfree(ctx, c->d_dir); dfree(ctx, c->d_dir_s); c->d_dir = c->d_dir_s = nullptr; return fail_hip(e, "coll_ensure_dir", __LINE__); }
+    d_optab.reset();
+    if (e != hipSuccess) return fail_hip(e, "coll_ensure_dir", __LINE__);
+    c->d_dir = (u32*)dir.release(); c->d_dir_s = (u32*)dir_s.release();
     dfree(ctx, c->d_bt); c->d_bt = nullptr; c->dir_pending = false;
     c->bytes += 2ull * dir_bytes; ctx->pack_bytes += 2ull * dir_bytes;
     return BMX_OK;
@@ -691,7 +699,7 @@ static int coll_members_launch(int mode, bmx_ctx* ctx, const bmx_coll* a, const 
 }
 
 // one arg-group for a one-shot call: member indices (A list, then S list) + the group record, staged to the device
-static int coll_members_upload(bmx_ctx* ctx, const std::vector<u32>& ma, const std::vector<u32>& ms, void** d_buf, const u32** d_midx, const CollGroup** d_groups);
+static int coll_members_upload(bmx_ctx* ctx, const std::vector<u32>& ma, const std::vector<u32>& ms, DevBuf& d_buf, const u32** d_midx, const CollGroup** d_groups);
 
 // Small host tables (operand pointer lists, pipeline metadata) go through a pinned ring: the copy is truly
 // asynchronous, the caller's buffer may die on return, and nobody has to synchronise the stream for it.  A region of
@@ -715,7 +723,7 @@ static int h2d_staged(bmx_ctx* ctx, void* dst, const void* src, size_t bytes)
     return BMX_OK;
 }
 
-static int coll_members_upload(bmx_ctx* ctx, const std::vector<u32>& ma, const std::vector<u32>& ms, void** d_buf, const u32** d_midx, const CollGroup** d_groups)
+static int coll_members_upload(bmx_ctx* ctx, const std::vector<u32>& ma, const std::vector<u32>& ms, DevBuf& d_buf, const u32** d_midx, const CollGroup** d_groups)
 {
     const size_t nm = ma.size() + ms.size(), goff = (nm * 4 + 15) & ~(size_t)15;
     std::vector<u8> h(goff + sizeof(CollGroup));
@@ -723,10 +731,9 @@ static int coll_members_upload(bmx_ctx* ctx, const std::vector<u32>& ma, const s
     if (!ms.empty()) memcpy(h.data() + ma.size() * 4, ms.data(), ms.size() * 4);
     const CollGroup g{0u, (u32)ma.size(), (u32)ma.size(), (u32)ms.size()};
     memcpy(h.data() + goff, &g, sizeof(g));
-    *d_buf = nullptr;
     int rc;
-    if ((rc = dmalloc(ctx, d_buf, h.size())) || (rc = h2d_staged(ctx, *d_buf, h.data(), h.size()))) { dfree(ctx, *d_buf); *d_buf = nullptr; return rc; }
-    *d_midx = (const u32*)*d_buf; *d_groups = (const CollGroup*)((const char*)*d_buf + goff);
+    if ((rc = dmalloc(ctx, &d_buf.p, h.size())) || (rc = h2d_staged(ctx, d_buf.p, h.data(), h.size()))) { d_buf.reset(); return rc; }
+    *d_midx = (const u32*)d_buf.p; *d_groups = (const CollGroup*)((const char*)d_buf.p + goff);
     return BMX_OK;
 }
 
@@ -826,115 +833,9 @@ static pipe_bits_fn pipe_bits_kernel(u32 rows, u32 unroll, bool nt, u32 wg)
     }
 }
 
-extern "C" {
-
-const char* bmx_error_msg(int status)
+// bmx_ctx_set_tuning, and bmx_ctx_create's environment knobs
+static int ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
 {
-    switch (status) {
-    case BMX_OK: return "BMX-00: All correct";
-    case BMX_ERR_BADALLOC: return "BMX-01: Allocation error (HBM or host)";
-    case BMX_ERR_BADARG: return "BMX-02: Invalid or missing function argument";
-    case BMX_ERR_RANGE: return "BMX-03: Incorrect range or index";
-    case BMX_ERR_DEVICE: return "BMX-04: No usable gfx950 device or HIP runtime failure";
-    default: return "BMX-XX: Unknown error";
-    }
-}
-const char* bmx_last_error(void) { return g_last_error.c_str(); }
-int bmx_simd_version(void) { return 950; }
-
-int bmx_device_count(int* n)
-{ ABI_TRY
-    ARGCHK(n);
-    *n = 0;
-    HIPCHK(hipGetDeviceCount(n));
-    return BMX_OK;
-ABI_END }
-
-int bmx_ctx_create(int device, void* stream, bmx_ctx** out)
-{ ABI_TRY
-    ARGCHK(out);
-    *out = nullptr;
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) { g_last_error = "device index out of range"; return BMX_ERR_RANGE; }
-    HIPCHK(hipSetDevice(device));
-    bmx_ctx* ctx = new (std::nothrow) bmx_ctx();
-    if (!ctx) return BMX_ERR_BADALLOC;
-    ctx->device = device;
-#define CTXCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = fail_hip(e_, #call, __LINE__); bmx_ctx_destroy(ctx); return r_; } } while (0)
-    if (stream) ctx->stream = (hipStream_t)stream;
-    else { CTXCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)); ctx->own_stream = true; }
-    CTXCHK(hipEventCreate(&ctx->ev0));
-    CTXCHK(hipEventCreate(&ctx->ev1));
-    CTXCHK(hipMalloc((void**)&ctx->d_small, 64 * sizeof(u64)));
-    CTXCHK(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(u64)));
-    CTXCHK(hipHostMalloc((void**)&ctx->h_stage, STAGE_BYTES));
-    CTXCHK(hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming));
-    CTXCHK(hipMalloc((void**)&ctx->d_slots, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64)));
-    CTXCHK(hipMemsetAsync(ctx->d_slots, 0, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64), ctx->stream));
-    CTXCHK(hipMalloc((void**)&ctx->d_zero, 256));
-    CTXCHK(hipMemsetAsync(ctx->d_zero, 0, 256, ctx->stream));
-    CTXCHK(hipMalloc((void**)&ctx->d_done, FOLD_DONE_WORDS * 4));
-    CTXCHK(hipMemsetAsync(ctx->d_done, 0, FOLD_DONE_WORDS * 4, ctx->stream));
-    CTXCHK(hipMalloc((void**)&ctx->d_slots2, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64)));
-    CTXCHK(hipMemsetAsync(ctx->d_slots2, 0, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64), ctx->stream));
-    CTXCHK(hipMalloc((void**)&ctx->d_done2, FOLD_DONE_WORDS * 4));
-    CTXCHK(hipMemsetAsync(ctx->d_done2, 0, FOLD_DONE_WORDS * 4, ctx->stream));
-    CTXCHK(hipHostMalloc((void**)&ctx->h_pend, PEND_SLOTS * 8 * sizeof(u64)));
-    CTXCHK(hipMalloc((void**)&ctx->d_cursor, 64));
-    CTXCHK(hipMemsetAsync(ctx->d_cursor, 0, 64, ctx->stream));
-#undef CTXCHK
-    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0) ctx->max_lds_bytes = (uint32_t)v; else (void)hipGetLastError(); }
-    { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr) ctx->pack_cap = (uint64_t)fr / 4; else (void)hipGetLastError(); }   // packed copies: at most a quarter of what is free now
-    if (const char* e = getenv("BMX_DEBUG_REDZONE")) ctx->redzone = atoi(e) != 0;
-    if (const char* e = getenv("BMX_PACK_MAX_MB")) { long long mb = atoll(e); if (mb >= 0) ctx->pack_cap = (uint64_t)mb << 20; }
-    if (const char* e = getenv("BMX_POOL_MAX_MB")) { long long mb = atoll(e); if (mb >= 0) ctx->pool_cap = (uint64_t)mb << 20; }
-    // launch-shape knobs from the environment go through the same validation as bmx_ctx_set_tuning;
-    // an invalid value is ignored (the default stays)
-    static const char* const env_keys[][2] = {
-        {"BMX_PIPE_UNROLL", "pipe_unroll"}, {"BMX_PIPE_ROWS", "pipe_rows"}, {"BMX_PIPE_NT", "pipe_nt"},
-        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}};
-    for (auto& kv : env_keys)
-        if (const char* e = getenv(kv[0])) (void)bmx_ctx_set_tuning(ctx, kv[1], atoi(e));
-    g_last_error.clear();
-    *out = ctx;
-    return BMX_OK;
-ABI_END }
-
-int bmx_ctx_destroy(bmx_ctx* ctx)
-{ ABI_TRY
-    if (!ctx) return BMX_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    while (!ctx->colls.empty()) coll_free(ctx, ctx->colls.size() - 1);
-    pool_trim(ctx);
-    // vectors / pipelines the caller never freed: their handles die with the context, the device memory must not leak
-    rz_verify(ctx, nullptr);
-    if (ctx->rz_hits) fprintf(stderr, "[bmx redzone] context destroyed with %llu damaged allocation(s) found during its life\n", (unsigned long long)ctx->rz_hits);
-    for (auto& kv : ctx->pool_live) { auto rz = ctx->rz_live.find(kv.first); (void)hipFree(rz != ctx->rz_live.end() ? rz->second.raw : kv.first); if (rz != ctx->rz_live.end()) ctx->rz_live.erase(rz); }
-    ctx->pool_live.clear();
-    ensure_release(ctx, &ctx->scratch, &ctx->scratch_bytes);
-    ensure_release(ctx, &ctx->aux, &ctx->aux_bytes);
-    if (ctx->d_small) (void)hipFree(ctx->d_small);
-    if (ctx->d_slots) (void)hipFree(ctx->d_slots);
-    if (ctx->d_done) (void)hipFree(ctx->d_done);
-    if (ctx->d_slots2) (void)hipFree(ctx->d_slots2);
-    if (ctx->d_done2) (void)hipFree(ctx->d_done2);
-    if (ctx->d_cursor) (void)hipFree(ctx->d_cursor);
-    if (ctx->h_pend) (void)hipHostFree(ctx->h_pend);
-    if (ctx->d_zero) (void)hipFree(ctx->d_zero);
-    if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-    return BMX_OK;
-ABI_END }
-
-int bmx_ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
-{ ABI_TRY
     ARGCHK(ctx && key);
     std::string k(key);
     if (k == "pipe_unroll") { ARGCHK(value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16); ctx->pipe_unroll = value; }
@@ -985,7 +886,159 @@ int bmx_ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
     else if (k == "xcd_swizzle") ctx->xcd_swz = value != 0;
     else { g_last_error = "unknown tuning key"; return BMX_ERR_BADARG; }
     return BMX_OK;
+}
+
+// releasing handles (bmx_internal.h).  stream_idle: no enqueued work may still read what goes (coll_drop_vector needs it too)
+static int stream_idle(bmx_ctx* ctx)
+{
+    int rc = set_dev(ctx); if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BMX_OK;
+}
+
+int vec_release(bmx_vec* v)
+{
+    bmx_ctx* ctx = v->ctx;
+    const int rc = stream_idle(ctx);
+    coll_drop_vector(ctx, v->uid);
+    ctx->live_vecs.erase(v->uid);
+    dfree(ctx, v->d_desc); dfree(ctx, v->d_bits); dfree(ctx, v->d_gaps); dfree(ctx, v->d_ord); dfree(ctx, v->d_tdir);
+    delete v;
+    return rc;
+}
+int rs_release(bmx_rs* rs)
+{
+    bmx_ctx* ctx = rs->ctx;
+    const int rc = stream_idle(ctx);
+    dfree(ctx, rs->d_bcount); dfree(ctx, rs->d_sub); dfree(ctx, rs->d_rcount); dfree(ctx, rs->d_cum); dfree(ctx, rs->d_gidx); dfree(ctx, rs->d_sample); dfree(ctx, rs->d_lines); dfree(ctx, rs->d_dir8); dfree(ctx, rs->d_sdir); dfree(ctx, rs->d_stop); dfree(ctx, rs->d_sel);
+    delete rs;
+    return rc;
+}
+int pipeline_release(bmx_pipeline* p)
+{
+    bmx_ctx* ctx = p->ctx;
+    const int rc = stream_idle(ctx);
+    dfree(ctx, p->d_dmat); dfree(ctx, p->d_meta); dfree(ctx, (void*)p->d_descs);
+    dfree(ctx, (void*)p->d_udesc); dfree(ctx, p->d_unblk); dfree(ctx, p->d_gmask); dfree(ctx, p->d_gskip);
+    dfree(ctx, p->cm_buf);
+    delete p;
+    return rc;
+}
+int pending_release(bmx_pending* p)
+{
+    bmx_ctx* ctx = p->ctx;
+    if (p->ev) (void)hipEventDestroy(p->ev);
+    if (p->slot >= 0) ctx->pend_used[p->slot >> 6] &= ~(1ull << (p->slot & 63));
+    dfree(ctx, p->scratch);
+    const int rc = p->v ? vec_release(p->v) : BMX_OK;
+    delete p;
+    return rc;
+}
+void ctx_release(bmx_ctx* ctx)
+{
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    while (!ctx->colls.empty()) coll_free(ctx, ctx->colls.size() - 1);
+    pool_trim(ctx);
+    // vectors / pipelines the caller never freed: their handles die with the context, the device memory must not leak
+    rz_verify(ctx, nullptr);
+    if (ctx->rz_hits) fprintf(stderr, "[bmx redzone] context destroyed with %llu damaged allocation(s) found during its life\n", (unsigned long long)ctx->rz_hits);
+    for (auto& kv : ctx->pool_live) { auto rz = ctx->rz_live.find(kv.first); (void)hipFree(rz != ctx->rz_live.end() ? rz->second.raw : kv.first); if (rz != ctx->rz_live.end()) ctx->rz_live.erase(rz); }
+    ctx->pool_live.clear();
+    ensure_release(ctx, &ctx->scratch, &ctx->scratch_bytes);
+    ensure_release(ctx, &ctx->aux, &ctx->aux_bytes);
+    if (ctx->d_small) (void)hipFree(ctx->d_small);
+    if (ctx->d_slots) (void)hipFree(ctx->d_slots);
+    if (ctx->d_done) (void)hipFree(ctx->d_done);
+    if (ctx->d_slots2) (void)hipFree(ctx->d_slots2);
+    if (ctx->d_done2) (void)hipFree(ctx->d_done2);
+    if (ctx->d_cursor) (void)hipFree(ctx->d_cursor);
+    if (ctx->h_pend) (void)hipHostFree(ctx->h_pend);
+    if (ctx->d_zero) (void)hipFree(ctx->d_zero);
+    if (ctx->h_small) (void)hipHostFree(ctx->h_small);
+    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
+    if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
+    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
+    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    delete ctx;
+}
+
+extern "C" {
+
+const char* bmx_error_msg(int status)
+{
+    switch (status) {
+    case BMX_OK: return "BMX-00: All correct";
+    case BMX_ERR_BADALLOC: return "BMX-01: Allocation error (HBM or host)";
+    case BMX_ERR_BADARG: return "BMX-02: Invalid or missing function argument";
+    case BMX_ERR_RANGE: return "BMX-03: Incorrect range or index";
+    case BMX_ERR_DEVICE: return "BMX-04: No usable gfx950 device or HIP runtime failure";
+    default: return "BMX-XX: Unknown error";
+    }
+}
+const char* bmx_last_error(void) { return g_last_error.c_str(); }
+int bmx_simd_version(void) { return 950; }
+
+int bmx_device_count(int* n)
+{ ABI_TRY
+    ARGCHK(n);
+    *n = 0;
+    HIPCHK(hipGetDeviceCount(n));
+    return BMX_OK;
 ABI_END }
+
+int bmx_ctx_create(int device, void* stream, bmx_ctx** out)
+{ ABI_TRY
+    ARGCHK(out);
+    *out = nullptr;
+    int n = 0;
+    HIPCHK(hipGetDeviceCount(&n));
+    if (device < 0 || device >= n) { g_last_error = "device index out of range"; return BMX_ERR_RANGE; }
+    HIPCHK(hipSetDevice(device));
+    Owned<bmx_ctx> ctx(new bmx_ctx());
+    ctx->device = device;
+    if (stream) ctx->stream = (hipStream_t)stream;
+    else { HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)); ctx->own_stream = true; }
+    HIPCHK(hipEventCreate(&ctx->ev0));
+    HIPCHK(hipEventCreate(&ctx->ev1));
+    HIPCHK(hipMalloc((void**)&ctx->d_small, 64 * sizeof(u64)));
+    HIPCHK(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(u64)));
+    HIPCHK(hipHostMalloc((void**)&ctx->h_stage, STAGE_BYTES));
+    HIPCHK(hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming));
+    HIPCHK(hipMalloc((void**)&ctx->d_slots, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64)));
+    HIPCHK(hipMemsetAsync(ctx->d_slots, 0, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64), ctx->stream));
+    HIPCHK(hipMalloc((void**)&ctx->d_zero, 256));
+    HIPCHK(hipMemsetAsync(ctx->d_zero, 0, 256, ctx->stream));
+    HIPCHK(hipMalloc((void**)&ctx->d_done, FOLD_DONE_WORDS * 4));
+    HIPCHK(hipMemsetAsync(ctx->d_done, 0, FOLD_DONE_WORDS * 4, ctx->stream));
+    HIPCHK(hipMalloc((void**)&ctx->d_slots2, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64)));
+    HIPCHK(hipMemsetAsync(ctx->d_slots2, 0, COUNT_SLOTS * COUNT_SLOT_STRIDE * sizeof(u64), ctx->stream));
+    HIPCHK(hipMalloc((void**)&ctx->d_done2, FOLD_DONE_WORDS * 4));
+    HIPCHK(hipMemsetAsync(ctx->d_done2, 0, FOLD_DONE_WORDS * 4, ctx->stream));
+    HIPCHK(hipHostMalloc((void**)&ctx->h_pend, PEND_SLOTS * 8 * sizeof(u64)));
+    HIPCHK(hipMalloc((void**)&ctx->d_cursor, 64));
+    HIPCHK(hipMemsetAsync(ctx->d_cursor, 0, 64, ctx->stream));
+    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v > 0) ctx->max_lds_bytes = (uint32_t)v; else (void)hipGetLastError(); }
+    { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr) ctx->pack_cap = (uint64_t)fr / 4; else (void)hipGetLastError(); }   // packed copies: at most a quarter of what is free now
+    if (const char* e = getenv("BMX_DEBUG_REDZONE")) ctx->redzone = atoi(e) != 0;
+    if (const char* e = getenv("BMX_PACK_MAX_MB")) { long long mb = atoll(e); if (mb >= 0) ctx->pack_cap = (uint64_t)mb << 20; }
+    if (const char* e = getenv("BMX_POOL_MAX_MB")) { long long mb = atoll(e); if (mb >= 0) ctx->pool_cap = (uint64_t)mb << 20; }
+    // launch-shape knobs from the environment go through the same validation as bmx_ctx_set_tuning;
+    // an invalid value is ignored (the default stays)
+    static const char* const env_keys[][2] = {
+        {"BMX_PIPE_UNROLL", "pipe_unroll"}, {"BMX_PIPE_ROWS", "pipe_rows"}, {"BMX_PIPE_NT", "pipe_nt"},
+        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}};
+    for (auto& kv : env_keys)
+        if (const char* e = getenv(kv[0])) (void)ctx_set_tuning(ctx.get(), kv[1], atoi(e));
+    g_last_error.clear();
+    *out = ctx.release();
+    return BMX_OK;
+ABI_END }
+
+int bmx_ctx_destroy(bmx_ctx* ctx) { ABI_TRY if (ctx) ctx_release(ctx); return BMX_OK; ABI_END }
+
+int bmx_ctx_set_tuning(bmx_ctx* ctx, const char* key, int value) { ABI_TRY return ctx_set_tuning(ctx, key, value); ABI_END }
 
 // Measurement helper: ms of one pass of c = a & b over three buffers of `bytes` each, in the launch shape of k_op2_stream
 // (a wave per stretch of 8-KiB blocks, non-temporal 16-byte loads and stores): the yardstick bench.py --config 1 puts next
@@ -1077,19 +1130,18 @@ int bmx_debug_redzone_check(bmx_ctx* ctx, int* enabled, uint64_t* hits, char* re
 ABI_END }
 
 int bmx_debug_inject_failure(bmx_ctx* ctx, int kind, long long after)
-{ ABI_TRY
-    ARGCHK(kind >= 0 && kind <= 5 && after >= 0);
-    if (kind == 4) { ARGCHK(ctx); ctx->fail_dmalloc_after = after; return BMX_OK; }
+{ ABI_TRY_UNCOUNTED
+    ARGCHK(kind >= 0 && kind <= 6 && after >= 0);
+    if (kind == 4 || kind == 6) { ARGCHK(ctx); ctx->fail_dmalloc_after = after; ctx->fail_dmalloc_throws = kind == 6; return BMX_OK; }
     if (kind == 5) {                                             // red-zone self-test: one byte written just past the requested end of a fresh block
         ARGCHK(ctx && ctx->redzone);
         int rc = set_dev(ctx); if (rc) return rc;
-        void* d = nullptr;
-        if ((rc = dmalloc(ctx, &d, 1000 + (size_t)after))) return rc;
+        DevBuf d(ctx);
+        if ((rc = dmalloc(ctx, &d.p, 1000 + (size_t)after))) return rc;
         HIPCHK(hipMemsetAsync((u8*)d + rz_user_end(1000 + (size_t)after), 0, 1, ctx->stream));
-        dfree(ctx, d);
         return BMX_OK;
     }
-    if (kind == 0) { g_inject_after = -1; g_inject_kind = 0; if (ctx) ctx->fail_dmalloc_after = -1; return BMX_OK; }
+    if (kind == 0) { g_inject_after = -1; g_inject_kind = 0; if (ctx) { ctx->fail_dmalloc_after = -1; ctx->fail_dmalloc_throws = false; } return BMX_OK; }
     g_inject_kind = kind; g_inject_after = after;
     return BMX_OK;
 ABI_END }
@@ -1193,15 +1245,13 @@ ABI_END }
 // ---------------------------------------------------------------------------
 // vectors
 // ---------------------------------------------------------------------------
-static bmx_vec* vec_alloc_host(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks)
+static Owned<bmx_vec> vec_alloc_host(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks)
 {
-    bmx_vec* v = new (std::nothrow) bmx_vec();
-    if (!v) return nullptr;
-    memset(v, 0, sizeof(*v));
+    Owned<bmx_vec> v(new bmx_vec());
     static std::atomic<uint64_t> next_uid{1};
     v->uid = next_uid.fetch_add(1);
     v->ctx = ctx; v->nbits = nbits; v->nblocks = nblocks;
-    ctx->live_vecs[v->uid] = v;
+    ctx->live_vecs[v->uid] = v.get();
     return v;
 }
 
@@ -1238,18 +1288,7 @@ static int vec_build_tdir(bmx_ctx* ctx, bmx_vec* v)
     return BMX_OK;
 }
 
-int bmx_vec_free(bmx_ctx* ctx, bmx_vec* v)
-{ ABI_TRY
-    if (!v) return BMX_OK;
-    ARGCHK(ctx && v->ctx == ctx);
-    int rc = set_dev(ctx); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    coll_drop_vector(ctx, v->uid);
-    ctx->live_vecs.erase(v->uid);
-    dfree(ctx, v->d_desc); dfree(ctx, v->d_bits); dfree(ctx, v->d_gaps); dfree(ctx, v->d_ord); dfree(ctx, v->d_tdir);
-    delete v;
-    return BMX_OK;
-ABI_END }
+int bmx_vec_free(bmx_ctx* ctx, bmx_vec* v) { ABI_TRY if (!v) return BMX_OK; ARGCHK(ctx && v->ctx == ctx); return vec_release(v); ABI_END }
 
 int bmx_vec_upload(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks,
                    const uint8_t* kinds, const uint32_t* offs,
@@ -1285,10 +1324,8 @@ int bmx_vec_upload(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks,
         desc[nb] = gpad_words;                                 // destination word offset, turned into a descriptor below
         gpad_words += ((uint64_t)len + 1u + 7u) & ~7ull;
     }
-    bmx_vec* v = vec_alloc_host(ctx, nbits, nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
-#define UPCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = fail_hip(e_, #call, __LINE__); bmx_vec_free(ctx, v); return r_; } } while (0)
-    if ((rc = vec_alloc_device(v, n_bit_blocks, gpad_words))) { bmx_vec_free(ctx, v); return rc; }
+    Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
+    if ((rc = vec_alloc_device(v.get(), n_bit_blocks, gpad_words))) return rc;
     memcpy(v->counts, counts, sizeof(counts));
     for (uint32_t nb = 0; nb < nblocks; ++nb) {
         uint8_t k = kinds[nb];
@@ -1296,29 +1333,28 @@ int bmx_vec_upload(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks,
         else if (k == BMX_GAP) { u16 h = gap_slab[offs[nb]]; desc[nb] = DESC_MAKE_GAP(v->d_gaps + desc[nb], h >> 3, h & 1u); }
         else desc[nb] = DESC_MAKE(0, k);
     }
-    if (nblocks) UPCHK(hipMemcpyAsync(v->d_desc, desc.data(), (size_t)nblocks * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (n_bit_blocks) UPCHK(hipMemcpyAsync(v->d_bits, bit_slab, (size_t)n_bit_blocks * 8192, hipMemcpyHostToDevice, ctx->stream));
+    if (nblocks) HIPCHK(hipMemcpyAsync(v->d_desc, desc.data(), (size_t)nblocks * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n_bit_blocks) HIPCHK(hipMemcpyAsync(v->d_bits, bit_slab, (size_t)n_bit_blocks * 8192, hipMemcpyHostToDevice, ctx->stream));
     if (any_gap) {
         size_t raw_bytes = ((size_t)gap_words * 2 + 15u) & ~(size_t)15u, src_bytes = (size_t)nblocks * 4;
-        if ((rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, raw_bytes + src_bytes))) { bmx_vec_free(ctx, v); return rc; }
+        if ((rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, raw_bytes + src_bytes))) return rc;
         u16* d_raw = (u16*)ctx->scratch; u32* d_src = (u32*)((char*)ctx->scratch + raw_bytes);
-        UPCHK(hipMemcpyAsync(d_raw, gap_slab, (size_t)gap_words * 2, hipMemcpyHostToDevice, ctx->stream));
-        UPCHK(hipMemcpyAsync(d_src, gsrc.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
-        UPCHK(hipMemsetAsync(ctx->d_small, 0, 8, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_raw, gap_slab, (size_t)gap_words * 2, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_src, gsrc.data(), src_bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemsetAsync(ctx->d_small, 0, 8, ctx->stream));
         hipLaunchKernelGGL(k_gap_repack, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                            (const u16*)d_raw, (const u32*)d_src, (const u64*)v->d_desc, nblocks, ctx->d_small);
-        UPCHK(hipGetLastError());
-        UPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if ((rc = vec_build_tdir(ctx, v))) { (void)hipStreamSynchronize(ctx->stream); bmx_vec_free(ctx, v); return rc; }
-    UPCHK(hipStreamSynchronize(ctx->stream));
-#undef UPCHK
+    if ((rc = vec_build_tdir(ctx, v.get()))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     if (any_gap && ctx->h_small[0]) {
-        bmx_vec_free(ctx, v);
+        v.reset();
         g_last_error = "malformed GAP block (terminator / run ends not strictly ascending)";
         return BMX_ERR_RANGE;
     }
-    *out = v;
+    *out = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -1331,29 +1367,26 @@ static int vec_from_raw(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, int opti
     BlockStat* st = (BlockStat*)ctx->aux;
     u32* offs = (u32*)((char*)ctx->aux + (size_t)nblocks * sizeof(BlockStat));
     const uint4* raw = (const uint4*)ctx->scratch;
-    bmx_vec* v = vec_alloc_host(ctx, nbits, nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
-#define RAWCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = fail_hip(e_, #call, __LINE__); bmx_vec_free(ctx, v); return r_; } } while (0)
+    Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
     if (nblocks) {
         hipLaunchKernelGGL(k_block_stats, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, raw, nblocks, optimize, st);
-        RAWCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, st, nblocks, offs, ctx->d_small);
-        RAWCHK(hipGetLastError());
-        RAWCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        RAWCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     } else memset(ctx->h_small, 0, 6 * sizeof(u64));
     uint32_t n_bit = (uint32_t)ctx->h_small[0]; uint64_t gap_words = ctx->h_small[1];
     for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
-    if ((rc = vec_alloc_device(v, n_bit, gap_words))) { bmx_vec_free(ctx, v); return rc; }
+    if ((rc = vec_alloc_device(v.get(), n_bit, gap_words))) return rc;
     if (nblocks) {
         hipLaunchKernelGGL(k_emit_blocks, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                            raw, nblocks, st, offs, v->d_bits, v->d_gaps, v->d_desc);
-        RAWCHK(hipGetLastError());
-        if ((rc = vec_build_tdir(ctx, v))) { (void)hipStreamSynchronize(ctx->stream); bmx_vec_free(ctx, v); return rc; }
-        RAWCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipGetLastError());
+        if ((rc = vec_build_tdir(ctx, v.get()))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     }
-#undef RAWCHK
-    *out = v;
+    *out = v.release();
     return BMX_OK;
 }
 
@@ -1459,10 +1492,10 @@ static int vec_indices_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out
     const uint32_t nblocks = v->nblocks;
     if (!nblocks) return BMX_OK;
     if (width == 4 && (uint64_t)nblocks > 65536ull) { g_last_error = "32-bit positions cannot address this vector: use width 8"; return BMX_ERR_RANGE; }
-    u32* d_bc = nullptr; u64* d_rc = nullptr; void* d_out = nullptr;
-    if ((rc = dmalloc(ctx, (void**)&d_bc, (size_t)nblocks * 4)) || (rc = dmalloc(ctx, (void**)&d_rc, (size_t)nblocks * 8))) { dfree(ctx, d_bc); return rc; }
-    hipLaunchKernelGGL(k_block_counts, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks, d_bc);
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, nblocks, d_rc, ctx->d_small);
+    DevBuf d_bc(ctx), d_rc(ctx), host_out(ctx);
+    if ((rc = dmalloc(ctx, &d_bc.p, (size_t)nblocks * 4)) || (rc = dmalloc(ctx, &d_rc.p, (size_t)nblocks * 8))) return rc;
+    hipLaunchKernelGGL(k_block_counts, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)d_bc);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, nblocks, (u64*)d_rc, ctx->d_small);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1471,8 +1504,8 @@ static int vec_indices_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out
         *n = total;
         if (total > cap) { rc = BMX_ERR_RANGE; g_last_error = "output buffer too small for the positions (n holds the number needed)"; }
         else if (total) {
-            d_out = out_is_host ? nullptr : out;
-            if (out_is_host) rc = dmalloc(ctx, &d_out, (size_t)total * (size_t)width);
+            if (out_is_host) rc = dmalloc(ctx, &host_out.p, (size_t)total * (size_t)width);
+            void* d_out = out_is_host ? host_out.p : out;
             if (!rc) {
                 if (width == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_indices<u64>), dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                                                    (const u64*)v->d_desc, nblocks, (const u64*)d_rc, (u64*)d_out, total, 0ull);
@@ -1485,8 +1518,7 @@ static int vec_indices_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out
         }
     }
     if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); rc = fail_hip(e, "bmx_vec_to_indices", __LINE__); }
-    if (out_is_host) dfree(ctx, d_out);
-    dfree(ctx, d_bc); dfree(ctx, d_rc);
+    host_out.reset(); d_bc.reset(); d_rc.reset();
     return rc;
 }
 
@@ -1634,23 +1666,18 @@ int bmx_pipeline_create(bmx_ctx* ctx, const bmx_vec* const* and_list, const uint
         }
     }
     null_row_off = col_stride; col_stride += 2;               // the always-empty row behind the groups' rows (k_limit_null)
-#define PIPECHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = fail_hip(e_, #call, __LINE__); bmx_pipeline_destroy(ctx, p); return r_; } } while (0)
-    bmx_pipeline* p = new (std::nothrow) bmx_pipeline();
-    if (!p) return BMX_ERR_BADALLOC;
-    memset(p, 0, sizeof(*p));
-    p->search_limit = ~0ull; p->cm_gen = ~0ull; p->cm_tried_gen = ~0ull - 1;     // (the memset above wiped the member initialisers)
+    Owned<bmx_pipeline> p(new bmx_pipeline());
     p->ctx = ctx; p->ngroups = (uint32_t)ngroups; p->ncols = ncols; p->col_stride = col_stride; p->null_row_off = null_row_off; p->n_ops = (uint32_t)n_ops; p->has_gap = has_gap; p->has_bit = has_bit; p->gap_avg_words = gap_blocks_sum ? (uint32_t)(gap_words_sum / gap_blocks_sum) : 0u;
     p->nbits = max_bits;
-    p->h_row_off = new std::vector<u32>(row_off, row_off + ngroups);
-    p->h_and_n = new std::vector<u32>(m_and_n, m_and_n + ngroups);
-    p->h_sub_n = new std::vector<u32>(m_sub_n, m_sub_n + ngroups);
+    p->h_row_off.assign(row_off, row_off + ngroups);
+    p->h_and_n.assign(m_and_n, m_and_n + ngroups);
+    p->h_sub_n.assign(m_sub_n, m_sub_n + ngroups);
     if (has_gap && !has_bit && tot_and) {
         // GAP-only operands: remember WHICH vectors (uids, not pointers) so that a run can be served by the packed collections
         // that hold them (the reference's pipeline keeps bvector pointers, :2939; here a freed vector is just not found)
-        p->h_uids = new std::vector<uint64_t>();
-        p->h_uids->reserve(tot_and + tot_sub);
-        for (size_t i = 0; i < tot_and; ++i) p->h_uids->push_back(and_list[i]->uid);
-        for (size_t i = 0; i < tot_sub; ++i) p->h_uids->push_back(sub_list[i]->uid);
+        p->h_uids.reserve(tot_and + tot_sub);
+        for (size_t i = 0; i < tot_and; ++i) p->h_uids.push_back(and_list[i]->uid);
+        for (size_t i = 0; i < tot_sub; ++i) p->h_uids.push_back(sub_list[i]->uid);
     }
     // distinct vectors of the pipeline (pipeline::unique_vectors(), src/bmaggregator.h:301) and the
     // (AND | SUB << 16) plane masks of every group, 16 planes per chunk -- only where the staged kernel can be chosen
@@ -1681,19 +1708,19 @@ int bmx_pipeline_create(bmx_ctx* ctx, const bmx_vec* const* and_list, const uint
                 a0 += and_n[g]; s0 += sub_n[g];
             }
             if ((rc = dmalloc(ctx, (void**)&p->d_udesc, udesc.size() * 8)) || (rc = dmalloc(ctx, (void**)&p->d_unblk, unblk.size() * 4)) ||
-                (rc = dmalloc(ctx, (void**)&p->d_gmask, gmask.size() * 4)) || (rc = dmalloc(ctx, (void**)&p->d_gskip, gskip.size() * 4))) { bmx_pipeline_destroy(ctx, p); return rc; }
-            PIPECHK(hipMemcpyAsync(p->d_udesc, udesc.data(), udesc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-            PIPECHK(hipMemcpyAsync(p->d_unblk, unblk.data(), unblk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            PIPECHK(hipMemcpyAsync(p->d_gmask, gmask.data(), gmask.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            PIPECHK(hipMemcpyAsync(p->d_gskip, gskip.data(), gskip.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-            PIPECHK(hipStreamSynchronize(ctx->stream));     // the host vectors die at the end of this scope
+                (rc = dmalloc(ctx, (void**)&p->d_gmask, gmask.size() * 4)) || (rc = dmalloc(ctx, (void**)&p->d_gskip, gskip.size() * 4))) return rc;
+            HIPCHK(hipMemcpyAsync(p->d_udesc, udesc.data(), udesc.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(p->d_unblk, unblk.data(), unblk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(p->d_gmask, gmask.data(), gmask.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(p->d_gskip, gskip.data(), gskip.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));     // the host vectors die at the end of this scope
         }
     }
     size_t b_dmat = (size_t)std::max<uint32_t>(ncols, 1) * col_stride * 8, b_meta = meta.size() * 4, b_descs = descs.size() * 8;
     if ((rc = dmalloc(ctx, (void**)&p->d_dmat, b_dmat)) || (rc = dmalloc(ctx, (void**)&p->d_meta, b_meta)) ||
-        (rc = dmalloc(ctx, (void**)&p->d_descs, b_descs))) { bmx_pipeline_destroy(ctx, p); return rc; }
+        (rc = dmalloc(ctx, (void**)&p->d_descs, b_descs))) return rc;
     p->bytes = b_dmat + b_meta + b_descs;
-    if ((rc = h2d_staged(ctx, p->d_meta, meta.data(), b_meta)) || (rc = h2d_staged(ctx, (void*)p->d_descs, descs.data(), b_descs))) { bmx_pipeline_destroy(ctx, p); return rc; }
+    if ((rc = h2d_staged(ctx, p->d_meta, meta.data(), b_meta)) || (rc = h2d_staged(ctx, (void*)p->d_descs, descs.data(), b_descs))) return rc;
     if (ncols) {
         PipeOperands po;
         po.desc = (const u64* const*)p->d_descs;
@@ -1703,30 +1730,17 @@ int bmx_pipeline_create(bmx_ctx* ctx, const bmx_vec* const* and_list, const uint
         u64 nrows = (u64)ncols * ngroups;                  // one wave per (column, group) row
         hipLaunchKernelGGL(k_pipe_sort, dim3((u32)((nrows + 3) / 4)), dim3(256), 0, ctx->stream,
                            po, (u32)ngroups, ncols, col_stride, p->d_dmat);
-        PIPECHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_pipe_null_rows, dim3((ncols + 255u) / 256u), dim3(256), 0, ctx->stream, p->d_dmat, ncols, col_stride, null_row_off);
-        PIPECHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     // no synchronise: the tables went through the pinned ring and everything that uses the rows is ordered behind
     // k_pipe_sort on the context's stream
-    *out = p;
+    *out = p.release();
     return BMX_OK;
-#undef PIPECHK
 ABI_END }
 
-int bmx_pipeline_destroy(bmx_ctx* ctx, bmx_pipeline* p)
-{ ABI_TRY
-    if (!p) return BMX_OK;
-    ARGCHK(ctx && p->ctx == ctx);
-    int rc = set_dev(ctx); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dfree(ctx, p->d_dmat); dfree(ctx, p->d_meta); dfree(ctx, (void*)p->d_descs);
-    dfree(ctx, (void*)p->d_udesc); dfree(ctx, p->d_unblk); dfree(ctx, p->d_gmask); dfree(ctx, p->d_gskip);
-    dfree(ctx, p->cm_buf);
-    delete p->h_row_off; delete p->h_and_n; delete p->h_sub_n; delete p->h_uids; delete p->h_win_groups; delete p->h_stop;
-    delete p;
-    return BMX_OK;
-ABI_END }
+int bmx_pipeline_destroy(bmx_ctx* ctx, bmx_pipeline* p) { ABI_TRY if (!p) return BMX_OK; ARGCHK(ctx && p->ctx == ctx); return pipeline_release(p); ABI_END }
 
 static int pipe_range(const bmx_pipeline* p, uint32_t& nb_from, uint32_t& nb_to)
 {
@@ -1799,9 +1813,9 @@ static bmx_coll* coll_by_id(bmx_ctx* ctx, uint64_t id)
 static int pipe_resolve_colls(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, bmx_coll** a, bmx_coll** s)
 {
     *a = nullptr; *s = nullptr;
-    if (!p->h_uids || ctx->gap_pack == 0) return BMX_OK;
+    if (p->h_uids.empty() || ctx->gap_pack == 0) return BMX_OK;
     size_t tot_and = 0, tot_sub = 0;
-    for (u32 g = 0; g < p->ngroups; ++g) { tot_and += (*p->h_and_n)[g]; tot_sub += (*p->h_sub_n)[g]; }
+    for (u32 g = 0; g < p->ngroups; ++g) { tot_and += p->h_and_n[g]; tot_sub += p->h_sub_n[g]; }
     if (p->cm_gen != ctx->coll_gen || (may_build && ctx->gap_pack == 1 && !p->cm_a_id && p->cm_tried_gen != ctx->coll_gen)) {
         int rc;
         // (no synchronise: a pooled block is only ever handed to work enqueued behind its last reader on this stream, see dfree --
@@ -1811,7 +1825,7 @@ static int pipe_resolve_colls(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, bmx
         if (may_build && ctx->gap_pack == 1) p->cm_tried_gen = ~0ull;
         p->cm_a_id = p->cm_s_id = 0; p->cm_full = false;
         std::vector<u32> ma, ms; bool fa = false, fs = true;
-        const uint64_t* uids = p->h_uids->data();
+        const uint64_t* uids = p->h_uids.data();
         bmx_coll* ca = coll_cover(ctx, uids, tot_and, 0, &ma, &fa);
         bmx_coll* cs = (ca && tot_sub) ? coll_cover(ctx, uids + tot_and, tot_sub, 1, &ms, &fs) : nullptr;
         if (!ca && may_build && ctx->gap_pack == 1 && p->ngroups == 1 && tot_and >= 64) {
@@ -1833,9 +1847,8 @@ static int pipe_resolve_colls(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, bmx
         const bool whole = p->ngroups == 1 && fa && (!tot_sub || fs);
         if (ca && !whole && !coll_members_wanted(ctx, (uint64_t)p->gap_avg_words, 1, p->n_ops, p->ngroups)) ca = nullptr;      // (the table kernels serve these groups better)
         if (ca && (!tot_sub || cs)) {
-            p->cm_a_id = ca->id; p->cm_s_id = cs ? cs->id : 0;
-            p->cm_full = p->ngroups == 1 && fa && (!tot_sub || fs);
-            // member indices (AND lists of all groups, then SUB lists) + one CollGroup per arg-group
+            // member indices (AND lists of all groups, then SUB lists) + one CollGroup per arg-group.  The pipeline names the
+            // collections only once that table is on the device: a failed (or throwing) allocation leaves it on the table kernels
             const size_t goff = ((tot_and + tot_sub) * 4 + 15) & ~(size_t)15;
             std::vector<u8> h(goff + (size_t)p->ngroups * sizeof(CollGroup));
             if (tot_and) memcpy(h.data(), ma.data(), tot_and * 4);
@@ -1843,18 +1856,19 @@ static int pipe_resolve_colls(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, bmx
             CollGroup* gr = reinterpret_cast<CollGroup*>(h.data() + goff);
             u32 ao = 0, so = (u32)tot_and;
             for (u32 g = 0; g < p->ngroups; ++g) {
-                gr[g] = CollGroup{ao, (*p->h_and_n)[g], so, (*p->h_sub_n)[g]};
-                ao += (*p->h_and_n)[g]; so += (*p->h_sub_n)[g];
+                gr[g] = CollGroup{ao, p->h_and_n[g], so, p->h_sub_n[g]};
+                ao += p->h_and_n[g]; so += p->h_sub_n[g];
             }
-            if ((rc = dmalloc(ctx, &p->cm_buf, h.size())) || (rc = h2d_staged(ctx, p->cm_buf, h.data(), h.size()))) {
-                dfree(ctx, p->cm_buf); p->cm_buf = nullptr; p->cm_a_id = p->cm_s_id = 0; return rc;
-            }
-            p->cm_groups_off = goff;
+            DevBuf buf(ctx);
+            if ((rc = dmalloc(ctx, &buf.p, h.size())) || (rc = h2d_staged(ctx, buf.p, h.data(), h.size()))) return rc;
+            p->cm_buf = buf.release(); p->cm_groups_off = goff;
+            p->cm_a_id = ca->id; p->cm_s_id = cs ? cs->id : 0;
+            p->cm_full = p->ngroups == 1 && fa && (!tot_sub || fs);
         }
     }
     *a = coll_by_id(ctx, p->cm_a_id);
     *s = coll_by_id(ctx, p->cm_s_id);
-    if (!*a || (p->cm_s_id && !*s)) { *a = nullptr; *s = nullptr; return BMX_OK; }
+    if (!*a || (p->cm_s_id && !*s) || !p->cm_buf) { *a = nullptr; *s = nullptr; return BMX_OK; }
     (*a)->last_use = ++ctx->coll_tick; if (*s) (*s)->last_use = ctx->coll_tick;
     return BMX_OK;
 }
@@ -1885,7 +1899,7 @@ static int pipeline_run_counts_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_f
     u64 nitems64 = (u64)(nb_to - nb_from) * ngroups;
     if (!nitems64) return BMX_OK;
     const u32* row_off = gv ? gv->row_off : p->d_meta; const u32* and_n = gv ? gv->and_n : p->d_meta + p->ngroups; const u32* sub_n = gv ? gv->sub_n : p->d_meta + 2 * p->ngroups;
-    if (p->h_uids) {
+    if (!p->h_uids.empty()) {
         // GAP-only operands held by packed collections: the column regions of the collections instead of the operands' slabs
         bmx_coll *ca = nullptr, *cs = nullptr;
         if ((rc = pipe_resolve_colls(ctx, p, may_build, &ca, &cs))) return rc;
@@ -2003,7 +2017,7 @@ int bmx_pipeline_describe(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint3
     int rc = pipe_range(p, nb_from, nb_to); if (rc) return rc;
     u64 nitems64 = (u64)(nb_to - nb_from) * p->ngroups;
     bool reuse = p->ngroups >= 32 && (uint64_t)p->n_ops >= 8ull * p->nplanes;
-    if (p->h_uids && ctx->gap_pack != 0 && p->cm_gen == ctx->coll_gen && coll_by_id(ctx, p->cm_a_id) && (!p->cm_s_id || coll_by_id(ctx, p->cm_s_id))) {
+    if (!p->h_uids.empty() && ctx->gap_pack != 0 && p->cm_gen == ctx->coll_gen && coll_by_id(ctx, p->cm_a_id) && (!p->cm_s_id || coll_by_id(ctx, p->cm_s_id))) {
         if (p->cm_full) snprintf(buf, buf_len, "k_coll_apply<AND_COUNT,512> x 1 launch, %llu workgroups (packed collection of the operand set)", (unsigned long long)nitems64);
         else snprintf(buf, buf_len, "k_coll_members<AND_COUNT> x 1 launch, a wave per (column, group): %u x %u items (members of a packed collection)", nb_to - nb_from, p->ngroups);
     }
@@ -2059,9 +2073,7 @@ static int limit_counts_run(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
     uint32_t f = nb_from, t = nb_to;
     if ((rc = pipe_range(p, f, t))) return rc;
     const u32 ng = p->ngroups, ncols = t - f;
-    if (!p->h_win_groups) p->h_win_groups = new std::vector<uint32_t>();
-    if (!p->h_stop) p->h_stop = new std::vector<uint32_t>();
-    p->h_win_groups->clear(); p->h_stop->assign(ng, 0xFFFFFFFFu);
+    p->h_win_groups.clear(); p->h_stop.assign(ng, 0xFFFFFFFFu);
     u32 w = std::max<u32>(ncols / 64u, 16u), planned = 0;
     for (u32 c = 0, ww = w; c < ncols; c += ww, ww *= 4u) ++planned;
     p->last_windows_planned = std::max(planned, 1u); p->last_windows = 0;
@@ -2069,15 +2081,15 @@ static int limit_counts_run(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
     if (!ncols) return BMX_OK;
     // collections / staged tables in force (resolved once, before the first window)
     bmx_coll *ca = nullptr, *cs = nullptr;
-    if (p->h_uids && (rc = pipe_resolve_colls(ctx, p, true, &ca, &cs))) return rc;
+    if (!p->h_uids.empty() && (rc = pipe_resolve_colls(ctx, p, true, &ca, &cs))) return rc;
     CollPin pin; pin.pin(ca, cs);                              // (the member table captured below must stay what the windows resolve: no eviction mid-run)
     const bool have_cg = ca && !p->cm_full && p->cm_buf;
     const bool have_masks = p->staged_ok && p->d_gmask && p->d_gskip;
     const size_t nch = std::max<u32>(p->nchunks, 1u);
     // device state: totals, the window's compact counts, stop columns, two active lists, the compacted tables
     const size_t words = (size_t)ng * (2 + 2 + 1 + 2 + 3 + (have_cg ? 4 : 0) + (have_masks ? nch + 1 : 0)) + 16;
-    u32* buf = nullptr;
-    if ((rc = dmalloc(ctx, (void**)&buf, words * 4))) return rc;
+    DevBuf buf(ctx);
+    if ((rc = dmalloc(ctx, &buf.p, words * 4))) return rc;
     u64* d_tot = (u64*)buf; u64* d_cc = d_tot + ng;
     u32* d_stop = (u32*)(d_cc + ng); u32* d_act[2] = {d_stop + ng, d_stop + 2 * (size_t)ng};
     u32* d_ro = d_act[1] + ng; u32* d_an = d_ro + ng; u32* d_sn = d_an + ng;
@@ -2089,7 +2101,7 @@ static int limit_counts_run(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
     u32* d_nact = q;
     hipError_t e = hipMemsetAsync(d_tot, 0, (size_t)ng * 8, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_stop, 0xFF, (size_t)ng * 4, ctx->stream);
-    if (e != hipSuccess) { dfree(ctx, buf); return fail_hip(e, "limit_counts_run", __LINE__); }
+    if (e != hipSuccess) return fail_hip(e, "limit_counts_run", __LINE__);
     LimitTables lt{p->d_meta, p->d_meta + ng, p->d_meta + 2 * (size_t)ng, d_ro, d_an, d_sn,
                    have_cg ? (const CollGroup*)((const char*)p->cm_buf + p->cm_groups_off) : nullptr, d_cg,
                    have_masks ? (const u32*)p->d_gmask : nullptr, have_masks ? (const u32*)p->d_gskip : nullptr, d_gm, d_gs, (u32)nch};
@@ -2105,18 +2117,17 @@ static int limit_counts_run(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);        // (the word in pinned memory is all the host reads)
         if (e != hipSuccess) { rc = fail_hip(e, "k_limit_step", __LINE__); break; }
-        p->h_win_groups->push_back(n_active);
+        p->h_win_groups.push_back(n_active);
         ++p->last_windows;
         n_active = (u32)ctx->h_small[60];
         cur ^= 1; first = false;
     }
     if (!rc) {
-        e = hipMemcpyAsync(p->h_stop->data(), d_stop, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(p->h_stop.data(), d_stop, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && counts_out) e = hipMemcpyAsync(counts_out, d_tot, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = fail_hip(e, "limit_counts_run readback", __LINE__);
     } else (void)hipStreamSynchronize(ctx->stream);
-    dfree(ctx, buf);
     return rc;
 }
 
@@ -2133,14 +2144,14 @@ static int limit_counts_run_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from,
     HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)std::max(ng, 1u) * 8, ctx->stream));
     if (!ncols || !ng) return BMX_OK;
     bmx_coll *ca = nullptr, *cs = nullptr;
-    if (p->h_uids && (rc = pipe_resolve_colls(ctx, p, false, &ca, &cs))) return rc;
+    if (!p->h_uids.empty() && (rc = pipe_resolve_colls(ctx, p, false, &ca, &cs))) return rc;
     CollPin pin; pin.pin(ca, cs);
     const bool have_cg = ca && !p->cm_full && p->cm_buf;
     const bool have_masks = p->staged_ok && p->d_gmask && p->d_gskip;
     // totals, the window's counts, row offsets, (member ranges), (gskip)
     const size_t words = (size_t)ng * (2 + 2 + 1 + (have_cg ? 4 : 0) + (have_masks ? 1 : 0)) + 16;
-    u32* buf = nullptr;
-    if ((rc = dmalloc(ctx, (void**)&buf, words * 4))) return rc;
+    DevBuf buf(ctx);                                               // (pooled: handed only to work enqueued behind this run)
+    if ((rc = dmalloc(ctx, &buf.p, words * 4))) return rc;
     u64* d_tot = (u64*)buf; u64* d_cc = d_tot + ng;
     u32* d_ro = (u32*)(d_cc + ng);
     u32* q = d_ro + ng;
@@ -2152,7 +2163,7 @@ static int limit_counts_run_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from,
     if (e == hipSuccess) e = hipMemcpyAsync(d_ro, p->d_meta, (size_t)ng * 4, hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess && have_cg) e = hipMemcpyAsync(d_cg, (const char*)p->cm_buf + p->cm_groups_off, (size_t)ng * sizeof(CollGroup), hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess && have_masks) e = hipMemcpyAsync(d_gs, p->d_gskip, (size_t)ng * 4, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) { dfree(ctx, buf); return fail_hip(e, "limit_counts_run_dev", __LINE__); }
+    if (e != hipSuccess) return fail_hip(e, "limit_counts_run_dev", __LINE__);
     GroupView gv{d_ro, p->d_meta + ng, p->d_meta + 2 * (size_t)ng, ng, have_masks ? (const u32*)p->d_gmask : nullptr, d_gs, d_cg};
     u32 w = std::max<u32>(ncols / 64u, 16u);
     for (u32 c = 0; c < ncols && !rc; c += w, w *= 4u) {
@@ -2164,7 +2175,6 @@ static int limit_counts_run_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from,
         e = hipGetLastError();
         if (e != hipSuccess) { rc = fail_hip(e, "k_limit_null", __LINE__); break; }
     }
-    dfree(ctx, buf);                                               // (pooled: handed only to work enqueued behind this run)
     return rc;
 }
 
@@ -2174,8 +2184,8 @@ extern "C" {
 int bmx_pipeline_last_window_groups(const bmx_pipeline* p, uint32_t* out, uint32_t cap, uint32_t* n)
 { ABI_TRY
     ARGCHK(p && (out || !cap));
-    const uint32_t have = p->h_win_groups ? (uint32_t)p->h_win_groups->size() : 0u;
-    for (uint32_t i = 0; i < have && i < cap; ++i) out[i] = (*p->h_win_groups)[i];
+    const uint32_t have = (uint32_t)p->h_win_groups.size();
+    for (uint32_t i = 0; i < have && i < cap; ++i) out[i] = p->h_win_groups[i];
     if (n) *n = have;
     return BMX_OK;
 ABI_END }
@@ -2186,17 +2196,16 @@ int bmx_pipeline_run_counts(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
     int rc = set_dev(ctx); if (rc) return rc;
     p->last_windows = p->last_windows_planned = 1;
     if (p->search_limit != ~0ull) return limit_counts_run(ctx, p, nb_from, nb_to, counts_out);
-    u64* d_counts = nullptr;
+    u64* d_counts = ctx->d_small;
     size_t bytes = (size_t)p->ngroups * 8;
-    if (p->ngroups <= 64) d_counts = ctx->d_small;
-    else if ((rc = dmalloc(ctx, (void**)&d_counts, bytes))) return rc;
+    DevBuf buf(ctx);
+    if (p->ngroups > 64) { if ((rc = dmalloc(ctx, &buf.p, bytes))) return rc; d_counts = (u64*)buf; }
     rc = pipeline_run_counts_impl(ctx, p, nb_from, nb_to, d_counts, true);
     if (!rc) {
         hipError_t e = hipMemcpyAsync(counts_out, d_counts, bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = fail_hip(e, "counts readback", __LINE__);
     }
-    if (p->ngroups > 64) dfree(ctx, d_counts);
     return rc;
 ABI_END }
 
@@ -2225,7 +2234,7 @@ ABI_END }
 // materialised results: full-size slab (one slot per block column), see
 // store_result() in bmx_kernels2.h
 // ---------------------------------------------------------------------------
-static int result_begin(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, bmx_vec** out, BlockStat** st, u32** offs)
+static int result_begin(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, Owned<bmx_vec>* out, BlockStat** st, u32** offs)
 {
     int rc;
     // st[nblocks] + offs[nblocks] (+ nblocks words of slack behind them: round 4's candidate list lived there)
@@ -2233,13 +2242,12 @@ static int result_begin(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, bmx_vec*
     if ((rc = ensure(ctx, &ctx->aux, &ctx->aux_bytes, aux_need))) return rc;
     *st = (BlockStat*)ctx->aux;
     *offs = (u32*)((char*)ctx->aux + (size_t)nblocks * sizeof(BlockStat));
-    bmx_vec* v = vec_alloc_host(ctx, nbits, nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
+    Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
     size_t b_desc = (size_t)std::max<uint32_t>(nblocks, 1) * 8, b_bits = (size_t)nblocks * 8192;
-    if ((rc = dmalloc(ctx, (void**)&v->d_desc, b_desc)) || (rc = dmalloc(ctx, (void**)&v->d_bits, b_bits))) { bmx_vec_free(ctx, v); return rc; }
+    if ((rc = dmalloc(ctx, (void**)&v->d_desc, b_desc)) || (rc = dmalloc(ctx, (void**)&v->d_bits, b_bits))) return rc;
     v->n_bit = nblocks;
     v->bytes = std::max<size_t>(b_desc, 16) + std::max<size_t>(b_bits, 16);
-    *out = v;
+    *out = std::move(v);
     return BMX_OK;
 }
 
@@ -2304,13 +2312,12 @@ extern "C" {
 // block-for-block copy of a device vector (bvector::operator=): same kinds, own slabs
 static int vec_clone(bmx_ctx* ctx, const bmx_vec* a, bmx_vec** out)
 {
-    bmx_vec* v = vec_alloc_host(ctx, a->nbits, a->nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
+    Owned<bmx_vec> v = vec_alloc_host(ctx, a->nbits, a->nblocks);
     int rc;
     size_t b_bits = a->d_bits ? (size_t)a->n_bit * 8192 : 0, b_gaps = a->d_gaps ? (size_t)a->gap_words * 2 + 64 : 0;
     size_t b_desc = (size_t)std::max<uint32_t>(a->nblocks, 1) * 8;
     if ((rc = dmalloc(ctx, (void**)&v->d_desc, b_desc)) || (b_bits && (rc = dmalloc(ctx, (void**)&v->d_bits, b_bits))) ||
-        (b_gaps && (rc = dmalloc(ctx, (void**)&v->d_gaps, b_gaps)))) { bmx_vec_free(ctx, v); return rc; }
+        (b_gaps && (rc = dmalloc(ctx, (void**)&v->d_gaps, b_gaps)))) return rc;
     v->n_bit = a->d_bits ? a->n_bit : 0; v->gap_words = a->d_gaps ? a->gap_words : 0;
     memcpy(v->counts, a->counts, sizeof(v->counts));
     v->bytes = std::max<size_t>(b_desc, 16) + std::max<size_t>(b_bits, 16) + std::max<size_t>(b_gaps, 16);
@@ -2319,7 +2326,7 @@ static int vec_clone(bmx_ctx* ctx, const bmx_vec* a, bmx_vec** out)
     if (e == hipSuccess && b_gaps) e = hipMemcpyAsync(v->d_gaps, a->d_gaps, b_gaps, hipMemcpyDeviceToDevice, ctx->stream);
     v->ord_lazy = a->ord_lazy;
     if (e == hipSuccess && a->d_ord && a->nblocks) {
-        if ((rc = dmalloc(ctx, (void**)&v->d_ord, (size_t)a->nblocks * 4))) { bmx_vec_free(ctx, v); return rc; }
+        if ((rc = dmalloc(ctx, (void**)&v->d_ord, (size_t)a->nblocks * 4))) return rc;
         e = hipMemcpyAsync(v->d_ord, a->d_ord, (size_t)a->nblocks * 4, hipMemcpyDeviceToDevice, ctx->stream);
     }
     if (e == hipSuccess && a->nblocks) {
@@ -2328,9 +2335,9 @@ static int vec_clone(bmx_ctx* ctx, const bmx_vec* a, bmx_vec** out)
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { bmx_vec_free(ctx, v); return fail_hip(e, "vec_clone", __LINE__); }
+    if (e != hipSuccess) return fail_hip(e, "vec_clone", __LINE__);
     if (a->count_valid) { v->count = a->count; v->count_valid = true; }
-    *out = v;
+    *out = v.release();
     return BMX_OK;
 }
 
@@ -2410,19 +2417,19 @@ int bmx_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int opt_co
         // aliasing as the reference handles it up front: AND / OR of a vector with itself is a block-for-block copy
         // (src/bm.h:6191-6195, 5984-5988), XOR / SUB are empty (:6081, 6412); nothing is re-optimised
         if (op == BMX_AND || op == BMX_OR) return vec_clone(ctx, a, result);
-        bmx_vec* v; BlockStat* st; u32* offs;
+        Owned<bmx_vec> v; BlockStat* st; u32* offs;
         if ((rc = result_begin(ctx, nbits, nblocks, &v, &st, &offs))) return rc;
         if (nblocks) {
             hipError_t e = hipMemsetAsync(v->d_desc, 0, (size_t)nblocks * 8, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) { bmx_vec_free(ctx, v); return fail_hip(e, "bmx_op2", __LINE__); }
+            if (e != hipSuccess) return fail_hip(e, "bmx_op2", __LINE__);
         }
         v->counts[BMX_NULL] = nblocks;
         dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0;
-        *result = v;
+        *result = v.release();
         return BMX_OK;
     }
-    bmx_vec* v; BlockStat* st; u32* offs;
+    Owned<bmx_vec> v; BlockStat* st; u32* offs;
     if ((rc = result_begin(ctx, nbits, nblocks, &v, &st, &offs))) return rc;
     // no GAP block can come out (neither operand holds one, no re-compression): the kernel folds the kind counts itself
     // and the layout scan is skipped -- k_op2, one synchronise, done -- unless result blocks vanished (then the scan /
@@ -2450,11 +2457,11 @@ int bmx_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int opt_co
             emit = !opt_compress && !no_gap && nblocks <= 2000000u;
             if (emit) {
                 gap_bound = (a->counts[BMX_GAP] ? a->gap_words : 0) + (b->counts[BMX_GAP] ? b->gap_words : 0) + 8u;
-                if ((rc = dmalloc(ctx, (void**)&v->d_gaps, (size_t)gap_bound * 2 + 64))) { bmx_vec_free(ctx, v); return rc; }
+                if ((rc = dmalloc(ctx, (void**)&v->d_gaps, (size_t)gap_bound * 2 + 64))) return rc;
             }
             // the kinds are folded whatever the operands hold: when every block came out as a bit-block (OR / XOR of two 1 % vectors:
             // their GAP x GAP results pass the 1,276-run limit) there is nothing for the layout scan to lay out
-            op2_loop_launch(ctx, op, a, b, nblocks, opt_compress, v, st,
+            op2_loop_launch(ctx, op, a, b, nblocks, opt_compress, v.get(), st,
                             (emit || no_gap || op == BMX_OR || op == BMX_XOR) ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr},
                             emit ? offs : (u32*)nullptr, emit ? v->d_gaps : (u16*)nullptr);
             folded = emit || op == BMX_OR || op == BMX_XOR;                 // (with re-compression AND / SUB go straight to the layout scan, no extra synchronise)
@@ -2470,23 +2477,22 @@ int bmx_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int opt_co
         }
         hipError_t e = hipGetLastError();
         if (e == hipSuccess && (no_gap || folded)) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { bmx_vec_free(ctx, v); return fail_hip(e, "k_op2", __LINE__); }
+        if (e != hipSuccess) return fail_hip(e, "k_op2", __LINE__);
         if (emit) {
-            rc = op2_finish_laid_out(ctx, v, st, offs, gap_bound);
-            if (rc) { bmx_vec_free(ctx, v); return rc; }
-            *result = v;
+            if ((rc = op2_finish_laid_out(ctx, v.get(), st, offs, gap_bound))) return rc;
+            *result = v.release();
             return BMX_OK;
         }
         if ((no_gap || folded) && ctx->h_small[2 + BMX_GAP] == 0 && ctx->h_small[2 + BMX_BIT] == nblocks) {
             for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
             if (counted) { v->count = ctx->h_small[8]; v->count_valid = true; }
-            *result = v;
+            *result = v.release();
             return BMX_OK;
         }
     }
-    if ((rc = result_finish(ctx, v, st, offs))) { bmx_vec_free(ctx, v); return rc; }       // (synchronises: the folded count has arrived too)
+    if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;       // (synchronises: the folded count has arrived too)
     if (counted) { v->count = ctx->h_small[8]; v->count_valid = true; }
-    *result = v;
+    *result = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -2499,9 +2505,11 @@ int bmx_op2_count(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int 
     if (!result) return bmx_count_op2(ctx, op, a, b, count);
     int rc = bmx_op2(ctx, op, a, b, opt_compress, result);
     if (rc) return rc;
-    rc = bmx_count(ctx, *result, count);
-    if (rc) { bmx_vec_free(ctx, *result); *result = nullptr; }
-    return rc;
+    Owned<bmx_vec> r(*result);
+    *result = nullptr;
+    if ((rc = bmx_count(ctx, r.get(), count))) return rc;
+    *result = r.release();
+    return BMX_OK;
 ABI_END }
 
 // ---- asynchronous 3-operand operations (bmx_op2_dev / bmx_pending_wait / bmx_pending_free) ----
@@ -2528,9 +2536,8 @@ int bmx_op2_dev(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_pending* pa, c
     int slot = -1;
     for (int i = 0; i < PEND_SLOTS; ++i) if (!(ctx->pend_used[i >> 6] >> (i & 63) & 1ull)) { slot = i; break; }
     if (slot < 0) { g_last_error = "bmx_op2_dev: 1,024 unresolved results are outstanding (bmx_pending_wait / bmx_pending_free them)"; return BMX_ERR_RANGE; }
-    bmx_pending* p = new (std::nothrow) bmx_pending();
-    if (!p) return BMX_ERR_BADALLOC;
-    p->ctx = ctx; p->v = nullptr; p->slot = slot; p->ev = nullptr; p->gap_bound = 0; p->scratch = nullptr; p->resolved = false;
+    Owned<bmx_pending> p(new bmx_pending());
+    p->ctx = ctx;
     if (((a && a == b) || (pa && pa == pb)) && (op == BMX_AND || op == BMX_OR)) {
         // aliasing as the reference handles it up front (src/bm.h:6191-6195, 5984-5988): x & x, x | x are block-for-block copies,
         // nothing is re-classified.  An unresolved operand is waited for here (its kind counts are the copy's).
@@ -2539,42 +2546,43 @@ int bmx_op2_dev(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_pending* pa, c
         memcpy(cnt, src->counts, sizeof(cnt));
         if (pa && !pa->resolved) {
             hipError_t ew = hipEventSynchronize(pa->ev);
-            if (ew != hipSuccess) { delete p; return fail_hip(ew, "bmx_op2_dev (alias)", __LINE__); }
+            if (ew != hipSuccess) return fail_hip(ew, "bmx_op2_dev (alias)", __LINE__);
             const u64* ps = ctx->h_pend + (size_t)pa->slot * 8;
             for (int k = 0; k < 4; ++k) cnt[k] = (uint32_t)ps[k];
             used = ps[4] & 0xFFFFFFFFFFull;
         }
         bmx_vec* c = nullptr;
-        if ((rc = vec_clone(ctx, src, &c))) { delete p; return rc; }
+        if ((rc = vec_clone(ctx, src, &c))) return rc;
+        p->v = c;
         memcpy(c->counts, cnt, sizeof(cnt));
         c->count_valid = false;
         if (c->d_gaps) c->gap_words = used;                                  // (an unresolved source: its slab is sized at the bound, its data end at `used`)
         if (c->d_bits && c->n_bit == c->nblocks && cnt[BMX_BIT] < c->nblocks && !c->d_ord) c->ord_lazy = true;
         hipError_t ee = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
         if (ee == hipSuccess) ee = hipEventRecord(p->ev, ctx->stream);
-        if (ee != hipSuccess) { bmx_vec_free(ctx, c); delete p; return fail_hip(ee, "bmx_op2_dev (alias)", __LINE__); }
-        p->v = c; p->resolved = true; p->gap_bound = c->d_gaps ? c->gap_words : 0;
-        ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
-        *out = p;
+        if (ee != hipSuccess) return fail_hip(ee, "bmx_op2_dev (alias)", __LINE__);
+        p->resolved = true; p->gap_bound = c->d_gaps ? c->gap_words : 0;
+        p->slot = slot; ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
+        *out = p.release();
         return BMX_OK;
     }
-    bmx_vec* v; BlockStat* st; u32* offs;
-    if ((rc = result_begin(ctx, nbits, nblocks, &v, &st, &offs))) { delete p; return rc; }
+    Owned<bmx_vec> res; BlockStat* st; u32* offs;
+    if ((rc = result_begin(ctx, nbits, nblocks, &res, &st, &offs))) return rc;
+    bmx_vec* v = p->v = res.release();
     u16* gap_slab = nullptr;
     if (gap_bound && nblocks) {
         // this result's own st[] / offs[] / candidate list (the context's scratch is the next operation's) and its GAP slab
         const uint64_t bound = gap_bound + 8u;
-        if ((rc = dmalloc(ctx, &p->scratch, (size_t)nblocks * (sizeof(BlockStat) + 8) + 64)) || (rc = dmalloc(ctx, (void**)&gap_slab, (size_t)bound * 2 + 64))) {
-            dfree(ctx, p->scratch); bmx_vec_free(ctx, v); delete p; return rc;
-        }
+        if ((rc = dmalloc(ctx, &p->scratch, (size_t)nblocks * (sizeof(BlockStat) + 8) + 64)) || (rc = dmalloc(ctx, (void**)&v->d_gaps, (size_t)bound * 2 + 64))) return rc;
+        gap_slab = v->d_gaps;
         st = (BlockStat*)p->scratch; offs = (u32*)((char*)p->scratch + (size_t)nblocks * sizeof(BlockStat));
-        v->d_gaps = gap_slab; v->gap_words = bound; v->bytes += (size_t)bound * 2 + 64;
+        v->gap_words = bound; v->bytes += (size_t)bound * 2 + 64;
         p->gap_bound = bound;
     }
     u64* hs = ctx->h_pend + (size_t)slot * 8;
     for (int k = 0; k < 8; ++k) hs[k] = 0;
     hipError_t e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
-    if (e != hipSuccess) { dfree(ctx, p->scratch); bmx_vec_free(ctx, v); delete p; return fail_hip(e, "hipEventCreate", __LINE__); }
+    if (e != hipSuccess) return fail_hip(e, "hipEventCreate", __LINE__);
     const FoldOut fo{ctx->d_slots, ctx->d_done, hs};
     const bool same = (a && b && a == b) || (pa && pb && pa == pb);
     if (!nblocks) hs[BMX_NULL] = 0;
@@ -2601,10 +2609,9 @@ int bmx_op2_dev(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_pending* pa, c
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(p->ev, ctx->stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); (void)hipEventDestroy(p->ev); dfree(ctx, p->scratch); bmx_vec_free(ctx, v); delete p; return fail_hip(e, "bmx_op2_dev", __LINE__); }
-    ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
-    p->v = v;
-    *out = p;
+    if (e != hipSuccess) return fail_hip(e, "bmx_op2_dev", __LINE__);
+    p->slot = slot; ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
+    *out = p.release();
     return BMX_OK;
 ABI_END }
 
@@ -2614,13 +2621,11 @@ int bmx_pending_wait(bmx_ctx* ctx, bmx_pending* p, bmx_vec** out)
     *out = nullptr;
     int rc = set_dev(ctx); if (rc) return rc;
     HIPCHK(hipEventSynchronize(p->ev));
-    bmx_vec* v = p->v;
+    Owned<bmx_vec> v(p->v);
+    p->v = nullptr;
     if (p->resolved) {
-        ctx->pend_used[p->slot >> 6] &= ~(1ull << (p->slot & 63));
-        (void)hipEventDestroy(p->ev);
-        p->v = nullptr;
-        delete p;
-        *out = v;
+        (void)pending_release(p);
+        *out = v.release();
         return BMX_OK;
     }
     const u64* hs = ctx->h_pend + (size_t)p->slot * 8;
@@ -2629,49 +2634,32 @@ int bmx_pending_wait(bmx_ctx* ctx, bmx_pending* p, bmx_vec** out)
     const uint64_t used = hs[4] & 0xFFFFFFFFFFull, ncand = hs[4] >> 40, bound = p->gap_bound;
     const bool ok = (uint64_t)v->counts[0] + v->counts[1] + v->counts[2] + v->counts[3] == nblocks && ncand == v->counts[BMX_GAP] &&
                     used <= bound && (used == 0) == (ncand == 0);
-    ctx->pend_used[p->slot >> 6] &= ~(1ull << (p->slot & 63));
-    (void)hipEventDestroy(p->ev);
-    dfree(ctx, p->scratch);                                           // (the kernel that wrote it ran before the event)
-    p->v = nullptr;
-    delete p;
-    if (!ok) { (void)hipStreamSynchronize(ctx->stream); bmx_vec_free(ctx, v); g_last_error = "bmx_pending_wait: inconsistent fold of the result block kinds"; return BMX_ERR_DEVICE; }
+    (void)pending_release(p);                                         // (its scratch: the kernel that wrote it ran before the event)
+    if (!ok) { v.reset(); g_last_error = "bmx_pending_wait: inconsistent fold of the result block kinds"; return BMX_ERR_DEVICE; }
     if (bound) {
         v->bytes -= std::min<size_t>(v->bytes, (size_t)bound * 2 + 64);
-        if ((rc = gap_slab_trim(ctx, v, bound, used, 0))) { bmx_vec_free(ctx, v); return rc; }
+        if ((rc = gap_slab_trim(ctx, v.get(), bound, used, 0))) return rc;
     }
     // the slab, as result_finish treats it: nothing alive -> back to the pool; sparse -> the survivors into a right-sized slab
     // (ordinals from the descriptor table; enqueued, not waited for); nearly full -> kept, ordinals at the first download
     const uint32_t live = v->counts[BMX_BIT];
     if (live == 0) { dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0; }
     else if ((uint64_t)live * 8u < (uint64_t)nblocks * 7u) {
-        uint4* packed = nullptr; u32* ord = nullptr;
-        if ((rc = dmalloc(ctx, (void**)&packed, (size_t)live * 8192)) || (rc = dmalloc(ctx, (void**)&ord, (size_t)nblocks * 4))) {
-            dfree(ctx, packed); bmx_vec_free(ctx, v); return rc;
-        }
-        hipLaunchKernelGGL(k_ord_from_desc, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)v->d_desc, nblocks, ord);
+        DevBuf packed(ctx), ord(ctx);
+        if ((rc = dmalloc(ctx, &packed.p, (size_t)live * 8192)) || (rc = dmalloc(ctx, &ord.p, (size_t)nblocks * 4))) return rc;
+        hipLaunchKernelGGL(k_ord_from_desc, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)ord);
         hipLaunchKernelGGL(k_compact_bits, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                           (const uint4*)v->d_bits, nblocks, (const BlockStat*)nullptr, (const u32*)ord, packed, v->d_desc);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); dfree(ctx, packed); dfree(ctx, ord); bmx_vec_free(ctx, v); return fail_hip(e, "bmx_pending_wait (compaction)", __LINE__); }
-        dfree(ctx, ord); dfree(ctx, v->d_bits);                          // (stream-ordered, see dfree)
-        v->d_bits = packed; v->n_bit = live;
+                           (const uint4*)v->d_bits, nblocks, (const BlockStat*)nullptr, (const u32*)ord, (uint4*)packed, v->d_desc);
+        if (hipError_t e = hipGetLastError()) return fail_hip(e, "bmx_pending_wait (compaction)", __LINE__);
+        ord.reset(); dfree(ctx, v->d_bits);                              // (stream-ordered, see dfree)
+        v->d_bits = (uint4*)packed.release(); v->n_bit = live;
     } else if (live < nblocks) v->ord_lazy = true;
-    *out = v;
+    *out = v.release();
     return BMX_OK;
 ABI_END }
 
 int bmx_pending_free(bmx_ctx* ctx, bmx_pending* p)
-{ ABI_TRY
-    if (!p) return BMX_OK;
-    ARGCHK(ctx && p->ctx == ctx);
-    (void)hipEventSynchronize(p->ev);
-    (void)hipEventDestroy(p->ev);
-    ctx->pend_used[p->slot >> 6] &= ~(1ull << (p->slot & 63));
-    dfree(ctx, p->scratch);
-    int rc = p->v ? bmx_vec_free(ctx, p->v) : BMX_OK;
-    delete p;
-    return rc;
-ABI_END }
+{ ABI_TRY if (!p) return BMX_OK; ARGCHK(ctx && p->ctx == ctx); (void)hipEventSynchronize(p->ev); return pending_release(p); ABI_END }
 
 static int count_op2_launch(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, u64* out, bool out_is_host)
 {
@@ -2756,7 +2744,7 @@ static int use_direct(const bmx_ctx* ctx, uint32_t ncols, size_t n_ops)
 }
 
 // operand table on the device: n descriptor-table pointers, then n block counts (u32); one staged copy
-static int direct_table(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb, void** d_tab)
+static int direct_table(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb, DevBuf& d_tab)
 {
     size_t n = na + nb;
     std::vector<u64> tab(n + (n + 1) / 2);
@@ -2767,8 +2755,7 @@ static int direct_table(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const 
         tab[i] = (u64)(uintptr_t)o->d_desc; nb32[i] = o->nblocks;
     }
     int rc;
-    *d_tab = nullptr;
-    if ((rc = dmalloc(ctx, d_tab, tab.size() * 8)) || (rc = h2d_staged(ctx, *d_tab, tab.data(), tab.size() * 8))) { dfree(ctx, *d_tab); *d_tab = nullptr; }
+    if ((rc = dmalloc(ctx, &d_tab.p, tab.size() * 8)) || (rc = h2d_staged(ctx, d_tab.p, tab.data(), tab.size() * 8))) d_tab.reset();
     return rc;
 }
 
@@ -2844,18 +2831,18 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
         has_gap |= src[i]->counts[BMX_GAP] != 0;
         has_bit |= src[i]->counts[BMX_BIT] != 0;
     }
-    bmx_vec* v; BlockStat* st; u32* offs;
+    Owned<bmx_vec> v; BlockStat* st; u32* offs;
     bmx_coll* packed = nullptr; std::vector<u32> members; bool packed_full = false;
     CollPin pin;
     if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;      // empty list => cleared target (:1105)
     if (use_direct(ctx, ncols, n)) {
-        void* d_tab = nullptr;
-        if ((rc = direct_table(ctx, src, n, nullptr, 0, &d_tab))) { bmx_vec_free(ctx, v); return rc; }
-        rc = direct_launch(DIRECT_OR, ctx, d_tab, n, 0, 0u, ncols, opt_compress, v, st, 0, 0u, 0u);
-        if (!rc) rc = result_finish(ctx, v, st, offs);
+        DevBuf d_tab(ctx);
+        if ((rc = direct_table(ctx, src, n, nullptr, 0, d_tab))) return rc;
+        rc = direct_launch(DIRECT_OR, ctx, d_tab.p, n, 0, 0u, ncols, opt_compress, v.get(), st, 0, 0u, 0u);
+        if (!rc) rc = result_finish(ctx, v.get(), st, offs);
         else (void)hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_tab);
-        if (rc) { bmx_vec_free(ctx, v); return rc; }
+        d_tab.reset();
+        if (rc) return rc;
     } else if (n >= 16 && ncols && has_gap && !has_bit && (rc = coll_resolve(ctx, src, n, 1, 64, true, &packed, &members, &packed_full)) == BMX_OK && packed && !packed_full &&
                !(ctx->coll_members < 0 && n >= 64 && or_rows_wanted(ctx, src, n)) && coll_members_wanted_list(ctx, src, n)) {
         pin.pin(packed);                                       // (coll_members_upload allocates: the collection must outlive it)
@@ -2863,14 +2850,14 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
         // (k_coll_members, bmx_kernels8.h).  Sparse lists of >= 64 vectors take the row kernel below instead: a member's piece
         // of a column is ~26 bytes there, and reading them one by one (9.1 ms for 2,048 of configs[4]'s 4,096 vectors) loses
         // to the rows of 14 columns the vectors' own tile directories give (1.7 ms, profiles/r04i)
-        void* d_buf = nullptr; const u32* d_midx = nullptr; const CollGroup* d_groups = nullptr;
-        if ((rc = coll_members_upload(ctx, members, std::vector<u32>(), &d_buf, &d_midx, &d_groups))) { bmx_vec_free(ctx, v); return rc; }
-        rc = coll_members_launch(CM_OR_STORE, ctx, packed, nullptr, d_midx, d_groups, 1u, 0u, ncols, opt_compress, nullptr, v, st);
-        if (!rc) rc = result_finish(ctx, v, st, offs);
+        DevBuf d_buf(ctx); const u32* d_midx = nullptr; const CollGroup* d_groups = nullptr;
+        if ((rc = coll_members_upload(ctx, members, std::vector<u32>(), d_buf, &d_midx, &d_groups))) return rc;
+        rc = coll_members_launch(CM_OR_STORE, ctx, packed, nullptr, d_midx, d_groups, 1u, 0u, ncols, opt_compress, nullptr, v.get(), st);
+        if (!rc) rc = result_finish(ctx, v.get(), st, offs);
         else (void)hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_buf);
-        if (rc) { bmx_vec_free(ctx, v); return rc; }
-    } else if (rc) { bmx_vec_free(ctx, v); return rc;
+        d_buf.reset();
+        if (rc) return rc;
+    } else if (rc) { return rc;
     } else if (packed && packed_full) {
         pin.pin(packed);
         // GAP-only operands = ALL the vectors of a packed collection: one sequential stream per block column (bmx_kernels6.h)
@@ -2878,7 +2865,7 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
         // block turned out to be a bit-block (the OR of thousands of sparse vectors), the layout scan is skipped (one launch
         // window only: the fold's tickets count the workgroups of ONE launch)
         const bool fold = !opt_compress && ctx->coll_window == 0;
-        rc = coll_launch(COLL_OR, ctx, packed, nullptr, 0u, ncols, opt_compress, nullptr, v, st, 0u, 0xFFFFFFFFu,
+        rc = coll_launch(COLL_OR, ctx, packed, nullptr, 0u, ncols, opt_compress, nullptr, v.get(), st, 0u, 0xFFFFFFFFu,
                          fold ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr});
         bool done = false;
         if (!rc && fold) {
@@ -2889,10 +2876,10 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
                 done = true;
             }
         }
-        if (!rc && !done) rc = result_finish(ctx, v, st, offs);
+        if (!rc && !done) rc = result_finish(ctx, v.get(), st, offs);
         else if (rc) (void)hipStreamSynchronize(ctx->stream);
-        if (rc) { bmx_vec_free(ctx, v); return rc; }
-    } else if (rc) { bmx_vec_free(ctx, v); return rc;
+        if (rc) return rc;
+    } else if (rc) { return rc;
     } else if (n >= 64 && ncols && has_gap && !has_bit && or_rows_wanted(ctx, src, n)) {
         // many SPARSE GAP-only operands: rows of 16 block columns read through the vectors' tile directories (k_agg_or_rows,
         // bmx_kernels7.h); the kernel folds the block kinds and the popcount of its result (no layout scan when every block
@@ -2902,16 +2889,14 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
             const bmx_vec* o = src[i];
             // uploaded / imported / generated vectors carry their tile directory; a RESULT vector (or a clone) gets its own the
             // first time it is an operand here (the directory is a cache of the immutable vector's layout: logically const)
-            if (!o->d_tdir && (rc = vec_build_tdir(ctx, const_cast<bmx_vec*>(o)))) { (void)hipStreamSynchronize(ctx->stream); bmx_vec_free(ctx, v); return rc; }
+            if (!o->d_tdir && (rc = vec_build_tdir(ctx, const_cast<bmx_vec*>(o)))) return rc;
             if (!o->d_tdir) continue;                                          // NULL blocks only: contributes nothing
             tab.push_back((u64)(uintptr_t)o->d_tdir); tab.push_back((u64)(uintptr_t)o->d_gaps);
             tab.push_back((u64)(uintptr_t)o->d_desc); tab.push_back((u64)o->nblocks);
         }
         const u32 nops = (u32)(tab.size() / 4);
-        void* d_tab = nullptr;
-        if ((rc = dmalloc(ctx, &d_tab, std::max<size_t>(tab.size() * 8, 64))) || (rc = h2d_staged(ctx, d_tab, tab.data(), tab.size() * 8))) {
-            dfree(ctx, d_tab); bmx_vec_free(ctx, v); return rc;
-        }
+        DevBuf d_tab(ctx);
+        if ((rc = dmalloc(ctx, &d_tab.p, std::max<size_t>(tab.size() * 8, 64))) || (rc = h2d_staged(ctx, d_tab.p, tab.data(), tab.size() * 8))) return rc;
         const size_t lds = (size_t)ORR_TILE * 8192 + 64;
         const u32 ntiles = (ncols + ORR_TILE - 1) / ORR_TILE;
         auto rows = ctx->or_depth == 8 ? k_agg_or_rows<8> : k_agg_or_rows<4>;
@@ -2923,19 +2908,19 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_tab);
-        if (e != hipSuccess) { bmx_vec_free(ctx, v); return fail_hip(e, "bmx_agg_or (rows)", __LINE__); }
+        d_tab.reset();
+        if (e != hipSuccess) return fail_hip(e, "bmx_agg_or (rows)", __LINE__);
         const uint64_t total = ctx->h_small[8];
         if (ctx->h_small[2 + BMX_GAP] == 0 && ctx->h_small[2 + BMX_BIT] == ncols) {
             for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
-        } else if ((rc = result_finish(ctx, v, st, offs))) { bmx_vec_free(ctx, v); return rc; }
+        } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
         v->count = total; v->count_valid = true;
     } else if (n >= 64 && ncols && has_gap && !has_bit) {
         // many GAP-only operands: column-tile kernel straight from the descriptor tables (no sort pass)
-        void* d_descs = nullptr; void* d_nblk = nullptr;
-        if ((rc = dmalloc(ctx, &d_descs, n * 8)) || (rc = dmalloc(ctx, &d_nblk, n * 4))) { dfree(ctx, d_descs); bmx_vec_free(ctx, v); return rc; }
-        hipError_t e = hipMemcpyAsync(d_descs, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_nblk, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+        DevBuf d_descs(ctx), d_nblk(ctx);
+        if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4))) return rc;
+        hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
         size_t lds = (size_t)OR_TILE * 8192 + OR_TILE * 4;
         // or_tile: 0 = single-bit fast path (default), 1 = the round-1 run code, 2 = two operands per lane per step;
         // tuning build, or_window = -9: loads only (the memory floor of the access pattern)
@@ -2956,19 +2941,17 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
                 e = hipGetLastError();
             }
         }
-        if (e == hipSuccess) rc = result_finish(ctx, v, st, offs);
+        if (e == hipSuccess) rc = result_finish(ctx, v.get(), st, offs);
         else rc = fail_hip(e, "bmx_agg_or (tiled)", __LINE__);
         (void)hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_descs); dfree(ctx, d_nblk);
-        if (rc) { bmx_vec_free(ctx, v); return rc; }
+        d_descs.reset(); d_nblk.reset();
+        if (rc) return rc;
     } else if (n && ncols) {
-        void* d_descs = nullptr; void* d_nblk = nullptr; void* d_dmat = nullptr;
+        DevBuf d_descs(ctx), d_nblk(ctx), d_dmat(ctx);
         size_t b_dmat = (size_t)ncols * (n + 2) * 8;
-        if ((rc = dmalloc(ctx, &d_descs, n * 8)) || (rc = dmalloc(ctx, &d_nblk, n * 4)) || (rc = dmalloc(ctx, &d_dmat, b_dmat))) {
-            dfree(ctx, d_descs); dfree(ctx, d_nblk); bmx_vec_free(ctx, v); return rc;
-        }
-        hipError_t e = hipMemcpyAsync(d_descs, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_nblk, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+        if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4)) || (rc = dmalloc(ctx, &d_dmat.p, b_dmat))) return rc;
+        hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_or_sort, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream,
                                (const u64* const*)d_descs, (const u32*)d_nblk, (u32)n, ncols, (u64*)d_dmat);
@@ -2978,16 +2961,16 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
                                v->d_bits, v->d_desc, st);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) rc = result_finish(ctx, v, st, offs);
+        if (e == hipSuccess) rc = result_finish(ctx, v.get(), st, offs);
         else rc = fail_hip(e, "bmx_agg_or", __LINE__);
         (void)hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_descs); dfree(ctx, d_nblk); dfree(ctx, d_dmat);
-        if (rc) { bmx_vec_free(ctx, v); return rc; }
+        d_descs.reset(); d_nblk.reset(); d_dmat.reset();
+        if (rc) return rc;
     } else if (ncols) {
         HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)ncols * 8, ctx->stream));
         v->counts[BMX_NULL] = ncols;
     }
-    *result = v;
+    *result = v.release();
     return BMX_OK;
 }
 
@@ -2998,12 +2981,12 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
 // otherwise one launch of 256-thread workgroups (GAP operands park the accumulator in LDS: 8 KiB per wave).
 static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, bmx_vec* v, BlockStat* st, uint32_t nb_from, uint32_t nb_to)
 {
-    const u64* rows = p->d_dmat + (*p->h_row_off)[g];
+    const u64* rows = p->d_dmat + p->h_row_off[g];
     const u32* an = p->d_meta + p->ngroups + g;
     const u32* sn = p->d_meta + 2 * p->ngroups + g;
     const u32 ncols = p->ncols;
     hipError_t e = hipSuccess;
-    if (ncols && use_and_rows(ctx, p, (uint64_t)(*p->h_and_n)[g] + (*p->h_sub_n)[g])) {
+    if (ncols && use_and_rows(ctx, p, (uint64_t)p->h_and_n[g] + p->h_sub_n[g])) {
         // GAP-only operands: the union of 0-runs over the operands' own slabs, result block stored (bmx_kernels9.h)
         hipLaunchKernelGGL(and_rows_kernel<AR_STORE>(ctx), dim3(ncols), dim3((u32)ctx->and_rows_wg), 0, ctx->stream,
                            rows, p->d_meta /* row_off[0] = 0: rows already points at group g */, an, sn, p->col_stride, 1u, 0u, ncols, ctx->xcd_swz, (u64*)nullptr,
@@ -3011,7 +2994,7 @@ static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, b
         e = hipGetLastError();
         return e == hipSuccess ? BMX_OK : fail_hip(e, "k_agg_and_rows", __LINE__);
     }
-    if (ncols && use_gapcount(ctx, p, (*p->h_and_n)[g])) {
+    if (ncols && use_gapcount(ctx, p, p->h_and_n[g])) {
         // GAP-only operands, a long list: the counting formulation, one 1024-thread workgroup per column, result block stored
         size_t lds = (size_t)(16384 * 2 + 2048) * 4;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_pipe_counts_gapcount<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -3064,27 +3047,27 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
     uint64_t nbits = 0; uint32_t ncols = 0;
     for (size_t i = 0; i < n_and; ++i) { ARGCHK(src_and[i]); nbits = std::max(nbits, src_and[i]->nbits); ncols = std::max(ncols, src_and[i]->nblocks); }
     for (size_t i = 0; i < n_sub; ++i) { ARGCHK(src_sub[i]); nbits = std::max(nbits, src_sub[i]->nbits); ncols = std::max(ncols, src_sub[i]->nblocks); }
-    bmx_vec* v; BlockStat* st; u32* offs;
+    Owned<bmx_vec> v; BlockStat* st; u32* offs;
     if (!n_and) {                                               // empty AND group => cleared target (:1170-1174)
         if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
         if (ncols) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)ncols * 8, ctx->stream));
         v->counts[BMX_NULL] = ncols;
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        *result = v;
+        *result = v.release();
         return BMX_OK;
     }
     // small collection (few columns, many operands): one launch straight from the descriptor tables (k_direct)
     if (use_direct(ctx, ncols, n_and + n_sub)) {
-        void* d_tab = nullptr;
-        if ((rc = direct_table(ctx, src_and, n_and, src_sub, n_sub, &d_tab))) return rc;
-        if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) { dfree(ctx, d_tab); return rc; }
-        rc = direct_launch(DIRECT_AND_SUB, ctx, d_tab, n_and, n_sub, 0u, ncols, 1, v, st, 0, 0u, 0u);
-        if (!rc) rc = result_finish(ctx, v, st, offs);              // synchronises
+        DevBuf d_tab(ctx);
+        if ((rc = direct_table(ctx, src_and, n_and, src_sub, n_sub, d_tab))) return rc;
+        if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
+        rc = direct_launch(DIRECT_AND_SUB, ctx, d_tab.p, n_and, n_sub, 0u, ncols, 1, v.get(), st, 0, 0u, 0u);
+        if (!rc) rc = result_finish(ctx, v.get(), st, offs);              // synchronises
         else (void)hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_tab);
-        if (rc) { bmx_vec_free(ctx, v); return rc; }
+        d_tab.reset();
+        if (rc) return rc;
         if (any) *any = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
-        *result = v;
+        *result = v.release();
         return BMX_OK;
     }
     {
@@ -3105,27 +3088,28 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
         if (ca) {
             CollPin pin; pin.pin(ca, cs);                      // (result_begin / coll_members_upload allocate: no eviction from under the call)
             if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-            void* d_buf = nullptr;
-            if (full) rc = coll_launch(COLL_AND_STORE, ctx, ca, cs, 0u, ncols, 1, nullptr, v, st, 0u, 0xFFFFFFFFu);
+            DevBuf d_buf(ctx);
+            if (full) rc = coll_launch(COLL_AND_STORE, ctx, ca, cs, 0u, ncols, 1, nullptr, v.get(), st, 0u, 0xFFFFFFFFu);
             else {
                 const u32* d_midx = nullptr; const CollGroup* d_groups = nullptr;
-                rc = coll_members_upload(ctx, ma, ms, &d_buf, &d_midx, &d_groups);
-                if (!rc) rc = coll_members_launch(CM_AND_STORE, ctx, ca, cs, d_midx, d_groups, 1u, 0u, ncols, 1, nullptr, v, st);
+                rc = coll_members_upload(ctx, ma, ms, d_buf, &d_midx, &d_groups);
+                if (!rc) rc = coll_members_launch(CM_AND_STORE, ctx, ca, cs, d_midx, d_groups, 1u, 0u, ncols, 1, nullptr, v.get(), st);
             }
-            if (!rc) rc = result_finish(ctx, v, st, offs);
+            if (!rc) rc = result_finish(ctx, v.get(), st, offs);
             else (void)hipStreamSynchronize(ctx->stream);
-            dfree(ctx, d_buf);
-            if (rc) { bmx_vec_free(ctx, v); return rc; }
+            d_buf.reset();
+            if (rc) return rc;
             if (any) *any = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
-            *result = v;
+            *result = v.release();
             return BMX_OK;
         }
     }
     uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub;
-    bmx_pipeline* p = nullptr;
-    if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &p))) return rc;
-    if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) { bmx_pipeline_destroy(ctx, p); return rc; }
-    if (ncols && use_split(ctx, p, ncols)) {
+    bmx_pipeline* praw = nullptr;
+    if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw))) return rc;
+    Owned<bmx_pipeline> p(praw);
+    if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
+    if (ncols && use_split(ctx, p.get(), ncols)) {
         size_t lds = (size_t)SPLIT_WAVES * 8192;
         auto fn = k_pipe_split<2, SPLIT_WAVES>;
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -3136,12 +3120,12 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
             e = hipGetLastError();
         }
         if (e != hipSuccess) rc = fail_hip(e, "k_pipe_split", __LINE__);
-    } else if (ncols) rc = agg_and_sub_launch(ctx, p, 0u, v, st, 0u, 0xFFFFFFFFu);
-    if (!rc) rc = result_finish(ctx, v, st, offs);
-    bmx_pipeline_destroy(ctx, p);
-    if (rc) { bmx_vec_free(ctx, v); return rc; }
+    } else if (ncols) rc = agg_and_sub_launch(ctx, p.get(), 0u, v.get(), st, 0u, 0xFFFFFFFFu);
+    if (!rc) rc = result_finish(ctx, v.get(), st, offs);
+    p.reset();
+    if (rc) return rc;
     if (any) *any = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
-    *result = v;
+    *result = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -3168,8 +3152,7 @@ static int run_results_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
     { int rcr = pipe_range(p, nb_from, nb_to); if (rcr) return rcr; }
     ARGCHK(!or_target_in || or_target_in->ctx == ctx);
     int rc = set_dev(ctx); if (rc) return rc;
-    std::vector<bmx_vec*> res(p->ngroups, nullptr);
-    auto cleanup = [&]() { for (bmx_vec* r : res) if (r) bmx_vec_free(ctx, r); };
+    std::vector<Owned<bmx_vec>> res(p->ngroups);
     // set_search_count_limit applies whenever counts are computed, result vectors included (the test at src/bmaggregator.h:1362
     // sits in front of both branches): a counts run under the limit finds the column at which every group has enough, and the
     // group's vector is produced up to there -- its count is >= min(limit, true count), bits beyond are not searched
@@ -3178,30 +3161,29 @@ static int run_results_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
     const uint32_t nb_to_all = nb_to;
     for (uint32_t g = 0; g < p->ngroups; ++g) {
         if (counts_out) counts_out[g] = 0;
-        if (!(*p->h_and_n)[g] || !p->ncols) continue;                       // empty AND group: skipped (:1352)
-        nb_to = limited ? std::min(nb_to_all, (*p->h_stop)[g]) : nb_to_all;
-        bmx_vec* v; BlockStat* st; u32* offs;
-        if ((rc = result_begin(ctx, p->nbits, p->ncols, &v, &st, &offs))) { cleanup(); return rc; }
+        if (!p->h_and_n[g] || !p->ncols) continue;                       // empty AND group: skipped (:1352)
+        nb_to = limited ? std::min(nb_to_all, p->h_stop[g]) : nb_to_all;
+        Owned<bmx_vec> v; BlockStat* st; u32* offs;
+        if ((rc = result_begin(ctx, p->nbits, p->ncols, &v, &st, &offs))) return rc;
         bmx_coll *ca = nullptr, *cs = nullptr;
-        if (p->h_uids && nb_from == 0 && nb_to >= p->ncols && (rc = pipe_resolve_colls(ctx, p, false, &ca, &cs))) { bmx_vec_free(ctx, v); cleanup(); return rc; }
+        if (!p->h_uids.empty() && nb_from == 0 && nb_to >= p->ncols && (rc = pipe_resolve_colls(ctx, p, false, &ca, &cs))) return rc;
         if (ca) rc = coll_members_launch(CM_AND_STORE, ctx, ca, cs, (const u32*)p->cm_buf, (const CollGroup*)((const char*)p->cm_buf + p->cm_groups_off) + g,
-                                         1u, 0u, p->ncols, 1, nullptr, v, st);       // (the group's members inside the packed collections)
-        else rc = agg_and_sub_launch(ctx, p, g, v, st, nb_from, nb_to);
-        if (rc) { bmx_vec_free(ctx, v); cleanup(); return rc; }
-        if ((rc = result_finish(ctx, v, st, offs))) { bmx_vec_free(ctx, v); cleanup(); return rc; }
-        if (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP] == 0) { bmx_vec_free(ctx, v); continue; }   // nothing found: stays NULL (:1406)
-        res[g] = v;
-        if (counts_out && (rc = bmx_count(ctx, v, &counts_out[g]))) { cleanup(); return rc; }
+                                         1u, 0u, p->ncols, 1, nullptr, v.get(), st);       // (the group's members inside the packed collections)
+        else rc = agg_and_sub_launch(ctx, p, g, v.get(), st, nb_from, nb_to);
+        if (rc) return rc;
+        if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+        if (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP] == 0) continue;   // nothing found: stays NULL (:1406)
+        res[g] = std::move(v);
+        if (counts_out && (rc = bmx_count(ctx, res[g].get(), &counts_out[g]))) return rc;
     }
     if (or_target_out) {
         std::vector<const bmx_vec*> src;
         if (or_target_in) src.push_back(or_target_in);
-        for (bmx_vec* r : res) if (r) src.push_back(r);
+        for (const Owned<bmx_vec>& r : res) if (r) src.push_back(r.get());
         *or_target_out = nullptr;
-        if ((rc = agg_or_impl(ctx, src.data(), src.size(), 1 /* optimised at the end, :1440-1447 */, or_target_out))) { cleanup(); return rc; }
+        if ((rc = agg_or_impl(ctx, src.data(), src.size(), 1 /* optimised at the end, :1440-1447 */, or_target_out))) return rc;
     }
-    if (results_out) for (uint32_t g = 0; g < p->ngroups; ++g) results_out[g] = res[g];
-    else cleanup();
+    if (results_out) for (uint32_t g = 0; g < p->ngroups; ++g) results_out[g] = res[g].release();
     return BMX_OK;
 }
 
@@ -3238,34 +3220,33 @@ int bmx_pipeline_run_results_hint(bmx_ctx* ctx, bmx_pipeline* p, uint64_t from, 
         return run_results_impl(ctx, p, lo, hi, results_out, counts_out, or_target_in, or_target_out);
     }
     // one block, partly covered: evaluate the column, then AND with the bit range
-    std::vector<bmx_vec*> res(p->ngroups, nullptr);
-    int rc = run_results_impl(ctx, p, (uint32_t)nbf, (uint32_t)nbf + 1u, res.data(), nullptr, nullptr, nullptr);
+    std::vector<bmx_vec*> out(p->ngroups, nullptr);
+    int rc = run_results_impl(ctx, p, (uint32_t)nbf, (uint32_t)nbf + 1u, out.data(), nullptr, nullptr, nullptr);
     if (rc) return rc;
-    auto cleanup = [&]() { for (bmx_vec*& r : res) if (r) { bmx_vec_free(ctx, r); r = nullptr; } };
-    bmx_vec* mask = nullptr;
-    if ((rc = hint_mask_vector(ctx, p->nbits, p->ncols, from, to, &mask))) { cleanup(); return rc; }
+    std::vector<Owned<bmx_vec>> res(out.begin(), out.end());
+    bmx_vec* mask_raw = nullptr;
+    if ((rc = hint_mask_vector(ctx, p->nbits, p->ncols, from, to, &mask_raw))) return rc;
+    Owned<bmx_vec> mask(mask_raw);
     for (uint32_t g = 0; g < p->ngroups && !rc; ++g) {
         if (counts_out) counts_out[g] = 0;
         if (!res[g]) continue;
         bmx_vec* m = nullptr;
-        rc = bmx_op2(ctx, BMX_AND, res[g], mask, 1, &m);
-        bmx_vec_free(ctx, res[g]); res[g] = nullptr;
+        rc = bmx_op2(ctx, BMX_AND, res[g].get(), mask.get(), 1, &m);
+        res[g].reset(m);
         if (rc) break;
-        if (m->counts[BMX_FULL] + m->counts[BMX_BIT] + m->counts[BMX_GAP] == 0) { bmx_vec_free(ctx, m); continue; }
-        res[g] = m;
+        if (m->counts[BMX_FULL] + m->counts[BMX_BIT] + m->counts[BMX_GAP] == 0) { res[g].reset(); continue; }
         if (counts_out) rc = bmx_count(ctx, m, &counts_out[g]);
     }
-    bmx_vec_free(ctx, mask);
+    mask.reset();
     if (!rc && or_target_out) {
         std::vector<const bmx_vec*> src;
         if (or_target_in) src.push_back(or_target_in);
-        for (bmx_vec* r : res) if (r) src.push_back(r);
+        for (const Owned<bmx_vec>& r : res) if (r) src.push_back(r.get());
         *or_target_out = nullptr;
         rc = agg_or_impl(ctx, src.data(), src.size(), 1, or_target_out);
     }
-    if (rc) { cleanup(); return rc; }
-    if (results_out) for (uint32_t g = 0; g < p->ngroups; ++g) results_out[g] = res[g];
-    else cleanup();
+    if (rc) return rc;
+    if (results_out) for (uint32_t g = 0; g < p->ngroups; ++g) results_out[g] = res[g].release();
     return BMX_OK;
 ABI_END }
 
@@ -3310,21 +3291,22 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     if (direct) {
         // many operands: a workgroup of 8 waves per column straight from the descriptor tables (k_direct); 64 columns first
         // (a hit in the first blocks is answered after ~1/8 of what two workgroups per CU would read)
-        void* d_tab = nullptr;
-        if ((rc = direct_table(ctx, src_and, n_and, src_sub, n_sub, &d_tab))) return rc;
+        DevBuf d_tab(ctx);
+        if ((rc = direct_table(ctx, src_and, n_and, src_sub, n_sub, d_tab))) return rc;
         hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
         if (e == hipSuccess)
-            rc = windows(n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) { return direct_launch(DIRECT_FIND_FIRST, ctx, d_tab, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt); });
+            rc = windows(n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) { return direct_launch(DIRECT_FIND_FIRST, ctx, d_tab.p, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt); });
         if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
         hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_tab);
+        d_tab.reset();
         if (rc) return rc;
         if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, "bmx_find_first_and_sub", __LINE__);
         if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
         return BMX_OK;
     }
-    bmx_pipeline* p = nullptr;
-    if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &p))) return rc;
+    bmx_pipeline* praw = nullptr;
+    if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw))) return rc;
+    Owned<bmx_pipeline> p(praw);
     hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
     if (e == hipSuccess) {
         size_t lds = p->has_gap ? 4 * 2048 * 4 : 0;
@@ -3337,7 +3319,7 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     }
     if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    bmx_pipeline_destroy(ctx, p);
+    p.reset();
     if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, "bmx_find_first_and_sub", __LINE__);
     if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
@@ -3352,8 +3334,8 @@ int bmx_agg_and_sub_indices(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t 
     bmx_vec* t = nullptr; int any = 0;
     int rc = bmx_agg_and_sub(ctx, src_and, n_and, src_sub, n_sub, &t, &any);
     if (rc) return rc;
+    Owned<bmx_vec> owned(t);
     if (any) rc = bmx_vec_to_indices(ctx, t, width, out, cap, n);
-    bmx_vec_free(ctx, t);
     return rc;
 ABI_END }
 
@@ -3387,22 +3369,22 @@ static int shift_right_and_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t 
         descs[i] = src[i]->d_desc; nblk[i] = src[i]->nblocks;
         ncols = std::max(ncols, src[i]->nblocks); nbits = std::max(nbits, src[i]->nbits);
     }
-    bmx_vec* v = nullptr; BlockStat* st = nullptr; u32* offs = nullptr;
+    Owned<bmx_vec> v; BlockStat* st = nullptr; u32* offs = nullptr;
     if (result && (rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;   // empty list => cleared target (:2499)
     if (!n || !ncols) {
         if (v && ncols) {
             hipError_t e = hipMemsetAsync(v->d_desc, 0, (size_t)ncols * 8, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) { bmx_vec_free(ctx, v); return fail_hip(e, "bmx_agg_shift_right_and", __LINE__); }
+            if (e != hipSuccess) return fail_hip(e, "bmx_agg_shift_right_and", __LINE__);
             v->counts[BMX_NULL] = ncols;
         }
-        if (result) *result = v;
+        if (result) *result = v.release();
         return BMX_OK;
     }
-    void* d_descs = nullptr; void* d_nblk = nullptr;
-    if ((rc = dmalloc(ctx, &d_descs, n * 8)) || (rc = dmalloc(ctx, &d_nblk, n * 4))) { dfree(ctx, d_descs); if (v) bmx_vec_free(ctx, v); return rc; }
-    hipError_t e = hipMemcpyAsync(d_descs, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+    DevBuf d_descs(ctx), d_nblk(ctx);
+    if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4))) return rc;
+    hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
     size_t lds = 4 * 4096 * 4;
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_shift_right_and, dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
@@ -3419,15 +3401,15 @@ static int shift_right_and_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t 
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
     }
-    if (e == hipSuccess && result) rc = result_finish(ctx, v, st, offs);
+    if (e == hipSuccess && result) rc = result_finish(ctx, v.get(), st, offs);
     else if (e != hipSuccess) rc = fail_hip(e, "bmx_agg_shift_right_and", __LINE__);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);
     if (!rc && e2 != hipSuccess) rc = fail_hip(e2, "bmx_agg_shift_right_and", __LINE__);
-    dfree(ctx, d_descs); dfree(ctx, d_nblk);
-    if (rc) { if (v) bmx_vec_free(ctx, v); return rc; }
+    d_descs.reset(); d_nblk.reset();
+    if (rc) return rc;
     if (result) {
         if (found) *found = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
-        *result = v;
+        *result = v.release();
     } else {
         *count = ctx->h_small[0];
         if (found) *found = *count != 0;
@@ -3472,14 +3454,14 @@ static int slice_compare_impl(bmx_ctx* ctx, const bmx_vec* const* slices, size_t
     }
     const bool sgn = sign_mode != SIGN_NONE || pred == CMP_SRANGE;
     const bool two = pred == BMX_CMP_RANGE || pred == CMP_SRANGE;
-    bmx_vec* v = nullptr; BlockStat* st = nullptr; u32* offs = nullptr;
+    Owned<bmx_vec> v; BlockStat* st = nullptr; u32* offs = nullptr;
     if (result && (rc = result_begin(ctx, size, ncols, &v, &st, &offs))) return rc;
-    if (!ncols) { if (result) *result = v; return BMX_OK; }
-    void* d_descs = nullptr; void* d_nblk = nullptr;
+    if (!ncols) { if (result) *result = v.release(); return BMX_OK; }
+    DevBuf d_descs(ctx), d_nblk(ctx);
     size_t nal = std::max<size_t>(nslices, 1);
-    if ((rc = dmalloc(ctx, &d_descs, nal * 8)) || (rc = dmalloc(ctx, &d_nblk, nal * 4))) { dfree(ctx, d_descs); if (v) bmx_vec_free(ctx, v); return rc; }
-    hipError_t e = hipMemcpyAsync(d_descs, descs.data(), nal * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk, nblk.data(), nal * 4, hipMemcpyHostToDevice, ctx->stream);
+    if ((rc = dmalloc(ctx, &d_descs.p, nal * 8)) || (rc = dmalloc(ctx, &d_nblk.p, nal * 4))) return rc;
+    hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), nal * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), nal * 4, hipMemcpyHostToDevice, ctx->stream);
     u64* d_stat = plane_bytes ? ctx->d_small + 8 : nullptr;
     if (e == hipSuccess && d_stat) e = hipMemsetAsync(d_stat, 0, 8, ctx->stream);
     if (e == hipSuccess) {
@@ -3509,16 +3491,16 @@ static int slice_compare_impl(bmx_ctx* ctx, const bmx_vec* const* slices, size_t
         if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess && d_stat) e = hipMemcpyAsync(ctx->h_small + 8, d_stat, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && result) rc = result_finish(ctx, v, st, offs);
+    if (e == hipSuccess && result) rc = result_finish(ctx, v.get(), st, offs);
     else if (e != hipSuccess) rc = fail_hip(e, "bmx_slice_compare", __LINE__);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);
     if (!rc && e2 != hipSuccess) rc = fail_hip(e2, "bmx_slice_compare", __LINE__);
-    dfree(ctx, d_descs); dfree(ctx, d_nblk);
-    if (rc) { if (v) bmx_vec_free(ctx, v); return rc; }
+    d_descs.reset(); d_nblk.reset();
+    if (rc) return rc;
     if (plane_bytes) *plane_bytes = ctx->h_small[8];
     if (result) {
-        *result = v;
-        if (count) { rc = bmx_count(ctx, v, count); if (rc) return rc; }
+        *result = v.release();
+        if (count) { rc = bmx_count(ctx, *result, count); if (rc) return rc; }
     } else *count = ctx->h_small[0];
     return BMX_OK;
 }
@@ -3638,20 +3620,20 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
     if (uniq.empty() || !ncols) return BMX_OK;
     // planes holding GAP blocks are expanded to raw bits once (k_vec_expand); the others are read through their tables
     EqPlanes pl; memset(&pl, 0, sizeof(pl));
-    std::vector<void*> temps;
-    auto free_temps = [&]() { for (void* t : temps) dfree(ctx, t); };
+    std::vector<DevBuf> bufs;
+    bufs.reserve(nslices);
     for (size_t i = 0; i < nslices; ++i) {
         const bmx_vec* sv = slices[i];
         if (!sv) continue;
         pl.nblk[i] = sv->nblocks;
         if (sv->counts[BMX_GAP]) {
-            void* raw = nullptr;
-            if ((rc = dmalloc(ctx, &raw, (size_t)ncols * 8192))) { free_temps(); return rc; }
-            temps.push_back(raw);
+            bufs.emplace_back(ctx);
+            if ((rc = dmalloc(ctx, &bufs.back().p, (size_t)ncols * 8192))) return rc;
+            const uint4* raw = (const uint4*)bufs.back();
             hipLaunchKernelGGL(k_vec_expand, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, sv->d_desc, sv->nblocks, ncols, (uint4*)raw);
             hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); free_temps(); return fail_hip(e, "k_vec_expand", __LINE__); }
-            pl.raw[i] = (const uint4*)raw;
+            if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail_hip(e, "k_vec_expand", __LINE__); }
+            pl.raw[i] = raw;
         } else pl.desc[i] = sv->d_desc;
     }
     std::vector<uint64_t> ucount(uniq.size(), 0);
@@ -3674,11 +3656,11 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
                 while (keys[h]) h = h + 1u == tab ? 0u : h + 1u;
                 keys[h] = v; where[k] = h;
             }
-            void* d_tab = nullptr; void* d_cnt = nullptr;
-            if ((rc = dmalloc(ctx, &d_tab, (size_t)tab * 4)) || (rc = dmalloc(ctx, &d_cnt, (size_t)tab * 8))) { dfree(ctx, d_tab); break; }
+            DevBuf d_tab(ctx), d_cnt(ctx);
+            if ((rc = dmalloc(ctx, &d_tab.p, (size_t)tab * 4)) || (rc = dmalloc(ctx, &d_cnt.p, (size_t)tab * 8))) break;
             std::vector<uint64_t> scount(tab, 0);
-            rc = h2d_staged(ctx, d_tab, keys.data(), (size_t)tab * 4);
-            hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt, 0, (size_t)tab * 8, ctx->stream);
+            rc = h2d_staged(ctx, d_tab.p, keys.data(), (size_t)tab * 4);
+            hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt.p, 0, (size_t)tab * 8, ctx->stream);
             if (!rc && e == hipSuccess) {
                 // eq_big_shape: 0 = 512 threads, 16 KiB filter, 1,024-entry queues; 1 = 512 threads, 32 KiB filter, 512-entry queues;
                 // 2 = 768 threads with the registers held to 3 waves per SIMD (8 filter reads in flight instead of 32), 32 KiB + 512
@@ -3694,10 +3676,10 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
                     hipLaunchKernelGGL(eqfn, dim3(grid), dim3(wg), lds, ctx->stream, pl, (u32)nslices, ncols, size, (const u32*)d_tab, tab, (u64*)d_cnt);
                     e = hipGetLastError();
                 }
-                if (e == hipSuccess) e = hipMemcpyAsync(scount.data(), d_cnt, (size_t)tab * 8, hipMemcpyDeviceToHost, ctx->stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(scount.data(), d_cnt.p, (size_t)tab * 8, hipMemcpyDeviceToHost, ctx->stream);
             }
             hipError_t e2 = hipStreamSynchronize(ctx->stream);
-            dfree(ctx, d_tab); dfree(ctx, d_cnt);
+            d_tab.reset(); d_cnt.reset();
             if (!rc && (e != hipSuccess || e2 != hipSuccess)) rc = fail_hip(e != hipSuccess ? e : e2, "bmx_slice_eq_counts", __LINE__);
             if (!rc) for (uint32_t k = 0; k < nv; ++k) ucount[u0 + k] = scount[where[k]];
             continue;
@@ -3712,10 +3694,10 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
             while (keys[h]) h = (h + 1u) & (tab - 1u);
             keys[h] = v; idx[h] = (uint16_t)k;
         }
-        void* d_tab = nullptr; void* d_cnt = nullptr;
-        if ((rc = dmalloc(ctx, &d_tab, blob.size() * 4)) || (rc = dmalloc(ctx, &d_cnt, (size_t)nv * 8))) { dfree(ctx, d_tab); break; }
-        rc = h2d_staged(ctx, d_tab, blob.data(), blob.size() * 4);
-        hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt, 0, (size_t)nv * 8, ctx->stream);
+        DevBuf d_tab(ctx), d_cnt(ctx);
+        if ((rc = dmalloc(ctx, &d_tab.p, blob.size() * 4)) || (rc = dmalloc(ctx, &d_cnt.p, (size_t)nv * 8))) break;
+        rc = h2d_staged(ctx, d_tab.p, blob.data(), blob.size() * 4);
+        hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt.p, 0, (size_t)nv * 8, ctx->stream);
         if (!rc && e == hipSuccess) {
             size_t lds = (size_t)tab * 4 + (size_t)nv * 4 + EQ_FILTER_WORDS * 4 + 4 * EQ_QUEUE * 4 + (size_t)tab * 2;
             auto eqfn = nslices <= 16 ? k_slice_eq_counts<16> : k_slice_eq_counts<32>;
@@ -3726,14 +3708,14 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
                                    (const u32*)d_tab, (const u16*)((const u32*)d_tab + tab), tab, shift, nv, (u64*)d_cnt);
                 e = hipGetLastError();
             }
-            if (e == hipSuccess) e = hipMemcpyAsync(ucount.data() + u0, d_cnt, (size_t)nv * 8, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(ucount.data() + u0, d_cnt.p, (size_t)nv * 8, hipMemcpyDeviceToHost, ctx->stream);
         }
         hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        dfree(ctx, d_tab); dfree(ctx, d_cnt);
+        d_tab.reset(); d_cnt.reset();
         if (!rc && (e != hipSuccess || e2 != hipSuccess)) rc = fail_hip(e != hipSuccess ? e : e2, "bmx_slice_eq_counts", __LINE__);
     }
     (void)hipStreamSynchronize(ctx->stream);
-    free_temps();
+    bufs.clear();
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q) if (slot[q] >= 0) counts[q] = ucount[(size_t)slot[q]];
     return BMX_OK;
@@ -3747,30 +3729,27 @@ int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
     ARGCHK(ctx && v && out && v->ctx == ctx);
     *out = nullptr;
     int rc = set_dev(ctx); if (rc) return rc;
-    bmx_rs* rs = new (std::nothrow) bmx_rs();
-    if (!rs) return BMX_ERR_BADALLOC;
-    memset(rs, 0, sizeof(*rs));
+    Owned<bmx_rs> rs(new bmx_rs());
     rs->ctx = ctx; rs->nblocks = v->nblocks;
     uint32_t n = std::max<uint32_t>(v->nblocks, 1);
     size_t b1 = (size_t)n * 4, b2 = (size_t)n * 8, b3 = (size_t)n * 8, b4 = (size_t)n * 128;
     if ((rc = dmalloc(ctx, (void**)&rs->d_bcount, b1)) || (rc = dmalloc(ctx, (void**)&rs->d_sub, b2)) ||
         (rc = dmalloc(ctx, (void**)&rs->d_rcount, b3)) || (rc = dmalloc(ctx, (void**)&rs->d_cum, b4)) ||
-        (rc = dmalloc(ctx, (void**)&rs->d_gidx, b4))) { bmx_rs_free(ctx, rs); return rc; }
+        (rc = dmalloc(ctx, (void**)&rs->d_gidx, b4))) return rc;
     rs->bytes = b1 + b2 + b3 + 2 * b4;
     if (v->nblocks) {
-#define RSCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int r_ = fail_hip(e_, #call, __LINE__); bmx_rs_free(ctx, rs); return r_; } } while (0)
         hipLaunchKernelGGL(k_rs_build, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                            v->d_desc, v->nblocks, rs->d_bcount, rs->d_sub, rs->d_cum, rs->d_gidx);
-        RSCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, rs->d_bcount, v->nblocks, rs->d_rcount, ctx->d_small);
-        RSCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t shift = 0;
         while (((v->nblocks + (1u << shift) - 1u) >> shift) > 2048u) ++shift;
         rs->sample_shift = shift; rs->nsamples = (v->nblocks + (1u << shift) - 1u) >> shift;
-        if ((rc = dmalloc(ctx, (void**)&rs->d_sample, (size_t)rs->nsamples * 8))) { bmx_rs_free(ctx, rs); return rc; }
+        if ((rc = dmalloc(ctx, (void**)&rs->d_sample, (size_t)rs->nsamples * 8))) return rc;
         hipLaunchKernelGGL(k_rs_sample, dim3((rs->nsamples + 255) / 256), dim3(256), 0, ctx->stream,
                            rs->d_rcount, v->nblocks, shift, rs->nsamples, rs->d_sample);
-        RSCHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         // rank lines (bmx_kernels6.h): the vector once more, interleaved with its running counts -- one line per rank query.
         // Memory policy (rs_lines 1): they are built where they cost no more than 2 x what the vector itself holds on the
         // device, i.e. for vectors with bit-blocks in more than about half of their block columns (configs[3]'s 66%); a sparse vector (GAP / NULL / FULL blocks: a 4e9-bit
@@ -3782,14 +3761,14 @@ int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
         const bool want_lines = lines_fit && (ctx->rs_lines == 2 || (ctx->rs_lines == 1 && (double)lines_bytes <= 2.0 * (double)v->bytes));
         if (want_lines) {
             size_t bl = lines_bytes;
-            if ((rc = dmalloc(ctx, (void**)&rs->d_lines, bl)) || (rc = dmalloc(ctx, (void**)&rs->d_dir8, (size_t)v->nblocks * 16u))) { bmx_rs_free(ctx, rs); return rc; }
+            if ((rc = dmalloc(ctx, (void**)&rs->d_lines, bl)) || (rc = dmalloc(ctx, (void**)&rs->d_dir8, (size_t)v->nblocks * 16u))) return rc;
             rs->bytes += bl + (size_t)v->nblocks * 16u;
             hipLaunchKernelGGL(k_rs_lines, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                                v->d_desc, v->nblocks, (const u64*)rs->d_rcount, rs->d_lines, rs->d_dir8);
-            RSCHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
-        RSCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-        RSCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
         rs->count = ctx->h_small[0];
         if (rs->count && ctx->rs_select_sel != 0) {
             // select lines (bmx_kernels11.h): the ones' positions, 60 (16-bit offsets) or 30 (32-bit) per 128-byte line.  Memory
@@ -3802,22 +3781,22 @@ int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
                 const uint64_t nsel = (rs->count + K - 1u) / K;
                 const size_t sb = (size_t)nsel * SL_BYTES;
                 if (ctx->rs_select_sel == -1 && (double)sb > budget) break;
-                u8* d = nullptr;
-                if (dmalloc(ctx, (void**)&d, sb) != BMX_OK) break;           // (an optional index: the directory kernels serve)
-                RSCHK(hipMemsetAsync(ctx->d_small + 32, 0, 8, ctx->stream));
+                DevBuf d(ctx);
+                if (dmalloc(ctx, &d.p, sb) != BMX_OK) break;                 // (an optional index: the directory kernels serve)
+                HIPCHK(hipMemsetAsync(ctx->d_small + 32, 0, 8, ctx->stream));
                 if (bits == 16) {
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_build<u16>), dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, d);
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_build<u16>), dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, (u8*)d);
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_check<u16>), dim3((u32)((nsel + 255u) / 256u)), dim3(256), 0, ctx->stream, (const u8*)d, (u64)nsel, (u64)rs->count, (const u64*)rs->d_rcount, v->nblocks, (u32*)(ctx->d_small + 32));
                 } else {
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_build<u32>), dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, d);
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_build<u32>), dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, (u8*)d);
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_check<u32>), dim3((u32)((nsel + 255u) / 256u)), dim3(256), 0, ctx->stream, (const u8*)d, (u64)nsel, (u64)rs->count, (const u64*)rs->d_rcount, v->nblocks, (u32*)(ctx->d_small + 32));
                 }
                 hipError_t e_ = hipGetLastError();
                 if (e_ == hipSuccess) e_ = hipMemcpyAsync(ctx->h_small + 32, ctx->d_small + 32, 8, hipMemcpyDeviceToHost, ctx->stream);
                 if (e_ == hipSuccess) e_ = hipStreamSynchronize(ctx->stream);
-                if (e_ != hipSuccess) { dfree(ctx, d); int r_ = fail_hip(e_, "select lines", __LINE__); bmx_rs_free(ctx, rs); return r_; }
-                if (ctx->h_small[32] != 0) { dfree(ctx, d); continue; }      // a line spans >= 2^bits bits: the wider form
-                rs->d_sel = d; rs->sel_bits = (uint32_t)bits; rs->sel_lines = nsel; rs->bytes += sb;
+                if (e_ != hipSuccess) return fail_hip(e_, "select lines", __LINE__);
+                if (ctx->h_small[32] != 0) { d.reset(); continue; }          // a line spans >= 2^bits bits: the wider form
+                rs->d_sel = (u8*)d.release(); rs->sel_bits = (uint32_t)bits; rs->sel_lines = nsel; rs->bytes += sb;
             }
         }
         if (rs->d_lines && rs->count) {
@@ -3830,30 +3809,30 @@ int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
             }
             while (((rs->count >> sh) + 2ull) * 4ull > (8ull << 20) && sh < 24u) ++sh;
             rs->sdir_shift = sh; rs->sdir_entries = ((rs->count + (1ull << sh) - 1ull) >> sh) + 1ull;
-            if ((rc = dmalloc(ctx, (void**)&rs->d_sdir, (size_t)rs->sdir_entries * 4u + 16u))) { bmx_rs_free(ctx, rs); return rc; }
+            if ((rc = dmalloc(ctx, (void**)&rs->d_sdir, (size_t)rs->sdir_entries * 4u + 16u))) return rc;
             rs->bytes += (size_t)rs->sdir_entries * 4u;
             hipLaunchKernelGGL(k_rs_sdir, dim3((u32)((nlines + 255u) / 256u)), dim3(256), 0, ctx->stream,
                                (const u32*)rs->d_lines, (u64)nlines, (u64)rs->count, sh, rs->d_sdir, (u64)rs->sdir_entries);
-            RSCHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
             // the directory's summary for LDS (k_select_top): one entry per 2^stop_shift ones, at most 65,535 + the sentinel; an entry
             // is the position of its one to 1 / 2^fb of a line (fb <= 3: as fine as the 16-bit offsets of a group of 64 entries allow)
             uint32_t ssh = sh;
             while (((rs->count + (1ull << ssh) - 1ull) >> ssh) + 1ull > STOP_ENTRIES && ssh < 40u) ++ssh;
             const uint32_t n_top = (uint32_t)(((rs->count + (1ull << ssh) - 1ull) >> ssh) + 1ull);
-            u32* d_p8 = nullptr;
-            if (nlines < (1ull << 28) && dmalloc(ctx, (void**)&d_p8, (size_t)n_top * 4u + 64u) == BMX_OK) {
-                if ((rc = dmalloc(ctx, (void**)&rs->d_stop, STOP_BYTES + 64u))) { dfree(ctx, d_p8); bmx_rs_free(ctx, rs); return rc; }
+            DevBuf d_p8(ctx);
+            if (nlines < (1ull << 28) && dmalloc(ctx, &d_p8.p, (size_t)n_top * 4u + 64u) == BMX_OK) {
+                if ((rc = dmalloc(ctx, (void**)&rs->d_stop, STOP_BYTES + 64u))) return rc;
                 hipError_t e_ = hipMemsetAsync(rs->d_stop, 0, STOP_BYTES + 64u, ctx->stream);
                 if (e_ == hipSuccess) e_ = hipMemsetAsync(ctx->d_small + 32, 0, 8, ctx->stream);
                 if (e_ == hipSuccess) {
                     hipLaunchKernelGGL(k_rs_stop_pos, dim3((n_top + 255u) / 256u), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_sdir, (u64)rs->sdir_entries,
-                                       sh, ssh, n_top, (u64)rs->count, d_p8);
+                                       sh, ssh, n_top, (u64)rs->count, (u32*)d_p8);
                     hipLaunchKernelGGL(k_rs_stop_range, dim3((n_top / STOP_GROUP + 256u) / 256u), dim3(256), 0, ctx->stream, (const u32*)d_p8, n_top, (u32*)(ctx->d_small + 32));
                     e_ = hipGetLastError();
                 }
                 if (e_ == hipSuccess) e_ = hipMemcpyAsync(ctx->h_small + 32, ctx->d_small + 32, 8, hipMemcpyDeviceToHost, ctx->stream);
                 if (e_ == hipSuccess) e_ = hipStreamSynchronize(ctx->stream);
-                if (e_ != hipSuccess) { dfree(ctx, d_p8); int r_ = fail_hip(e_, "select summary", __LINE__); bmx_rs_free(ctx, rs); return r_; }
+                if (e_ != hipSuccess) return fail_hip(e_, "select summary", __LINE__);
                 const uint32_t spread = (uint32_t)ctx->h_small[32];          // in eighths of a line
                 uint32_t fb = 3u;
                 while (fb > 0u && (spread >> (3u - fb)) > 65000u) --fb;
@@ -3861,15 +3840,14 @@ int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
                 else {
                     hipLaunchKernelGGL(k_rs_stop_pack, dim3((n_top + 255u) / 256u), dim3(256), 0, ctx->stream, (const u32*)d_p8, n_top, 3u - fb, rs->d_stop, (u16*)(rs->d_stop + STOP_BASES));
                     e_ = hipGetLastError();
-                    if (e_ != hipSuccess) { dfree(ctx, d_p8); int r_ = fail_hip(e_, "k_rs_stop_pack", __LINE__); bmx_rs_free(ctx, rs); return r_; }
+                    if (e_ != hipSuccess) return fail_hip(e_, "k_rs_stop_pack", __LINE__);
                     rs->stop_shift = ssh; rs->stop_fb = fb; rs->bytes += STOP_BYTES;
                 }
-                dfree(ctx, d_p8);
+                d_p8.reset();
             }
         }
-#undef RSCHK
     }
-    *out = rs;
+    *out = rs.release();
     return BMX_OK;
 ABI_END }
 
@@ -3889,16 +3867,7 @@ int bmx_rs_select_format(const bmx_rs* rs, int* offset_bits, uint64_t* bytes)
     return BMX_OK;
 ABI_END }
 
-int bmx_rs_free(bmx_ctx* ctx, bmx_rs* rs)
-{ ABI_TRY
-    if (!rs) return BMX_OK;
-    ARGCHK(ctx && rs->ctx == ctx);
-    int rc = set_dev(ctx); if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    dfree(ctx, rs->d_bcount); dfree(ctx, rs->d_sub); dfree(ctx, rs->d_rcount); dfree(ctx, rs->d_cum); dfree(ctx, rs->d_gidx); dfree(ctx, rs->d_sample); dfree(ctx, rs->d_lines); dfree(ctx, rs->d_dir8); dfree(ctx, rs->d_sdir); dfree(ctx, rs->d_stop); dfree(ctx, rs->d_sel);
-    delete rs;
-    return BMX_OK;
-ABI_END }
+int bmx_rs_free(bmx_ctx* ctx, bmx_rs* rs) { ABI_TRY if (!rs) return BMX_OK; ARGCHK(ctx && rs->ctx == ctx); return rs_release(rs); ABI_END }
 
 int bmx_rs_count(const bmx_rs* rs, uint64_t* count) { ABI_TRY ARGCHK(rs && count); *count = rs->count; return BMX_OK; ABI_END }
 
@@ -4003,15 +3972,16 @@ int bmx_rank_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uint6
     ARGCHK(ctx && (q == 0 || (n && out)));
     int rc = set_dev(ctx); if (rc) return rc;
     if (!q) return BMX_OK;
-    u64* d = nullptr;
-    if ((rc = dmalloc(ctx, (void**)&d, q * 16))) return rc;
+    DevBuf buf(ctx);
+    if ((rc = dmalloc(ctx, &buf.p, q * 16))) return rc;
+    u64* d = (u64*)buf;
     hipError_t e = hipMemcpyAsync(d, n, q * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         rc = bmx_rank_batch_dev(ctx, v, rs, d, q, d + q);
         if (!rc) e = hipMemcpyAsync(out, d + q, q * 8, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(ctx, d);
+    buf.reset();
     if (e != hipSuccess) return fail_hip(e, "bmx_rank_batch", __LINE__);
     return rc;
 ABI_END }
@@ -4022,8 +3992,9 @@ int bmx_select_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uin
     ARGCHK(ctx && (q == 0 || (rank && pos && found)));
     int rc = set_dev(ctx); if (rc) return rc;
     if (!q) return BMX_OK;
-    u64* d = nullptr;
-    if ((rc = dmalloc(ctx, (void**)&d, q * 17))) return rc;
+    DevBuf buf(ctx);
+    if ((rc = dmalloc(ctx, &buf.p, q * 17))) return rc;
+    u64* d = (u64*)buf;
     hipError_t e = hipMemcpyAsync(d, rank, q * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         rc = bmx_select_batch_dev(ctx, v, rs, d, q, d + q, (uint8_t*)(d + 2 * q));
@@ -4031,7 +4002,7 @@ int bmx_select_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uin
         if (!rc && e == hipSuccess) e = hipMemcpyAsync(found, d + 2 * q, q, hipMemcpyDeviceToHost, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(ctx, d);
+    buf.reset();
     if (e != hipSuccess) return fail_hip(e, "bmx_select_batch", __LINE__);
     return rc;
 ABI_END }
@@ -4097,8 +4068,7 @@ static int distance_matrix_launch(bmx_ctx* ctx, const bmx_vec* const* a, size_t 
     if (d_cb && nb) HIPCHK(hipMemsetAsync(d_cb, 0, nb * 8, ctx->stream));
     if (!na || !nb) return BMX_OK;
     const size_t n = na + (sym ? 0 : nb);
-    std::vector<void*> temps;
-    auto cleanup = [&]() { for (void* p : temps) dfree(ctx, p); };
+    std::vector<DevBuf> bufs;                                        // the expanded copies, the operand table, the tile pairs
     // operand table; vectors holding GAP blocks get an expanded copy of their block table (one per distinct vector)
     std::vector<u64> tab(n + (n + 1) / 2, 0ull);
     u32* nblk = reinterpret_cast<u32*>(tab.data() + n);
@@ -4107,7 +4077,7 @@ static int distance_matrix_launch(bmx_ctx* ctx, const bmx_vec* const* a, size_t 
     for (size_t e = 0; e < n; ++e) {
         const bmx_vec* v = e < na ? a[e] : b[e - na];
         if (!v) continue;                                             // an absent vector: empty (build_jaccard_similarity_batch)
-        if (v->ctx != ctx) { cleanup(); g_last_error = "bad argument: an operand belongs to another context"; return BMX_ERR_BADARG; }
+        if (v->ctx != ctx) { g_last_error = "bad argument: an operand belongs to another context"; return BMX_ERR_BADARG; }
         ncols = std::max(ncols, v->nblocks);
         nblk[e] = v->nblocks;
         if (!v->nblocks) continue;
@@ -4116,21 +4086,19 @@ static int distance_matrix_launch(bmx_ctx* ctx, const bmx_vec* const* a, size_t 
         if (it != expanded.end()) { tab[e] = it->second; continue; }
         const size_t desc_bytes = ((size_t)v->nblocks * 8 + 255) & ~(size_t)255;
         const size_t slab_bytes = (size_t)v->counts[BMX_GAP] * 8192;
-        void* buf = nullptr;
-        if ((rc = dmalloc(ctx, &buf, desc_bytes + slab_bytes + 256))) { cleanup(); return rc; }
-        temps.push_back(buf);
-        char* p = (char*)buf;
+        bufs.emplace_back(ctx);
+        if ((rc = dmalloc(ctx, &bufs.back().p, desc_bytes + slab_bytes + 256))) return rc;
+        char* p = (char*)bufs.back().p;
         u32* cursor = (u32*)(p + desc_bytes + slab_bytes);
-        if (hipError_t e2 = hipMemsetAsync(cursor, 0, 4, ctx->stream)) { cleanup(); return fail_hip(e2, "hipMemsetAsync", __LINE__); }
+        if (hipError_t e2 = hipMemsetAsync(cursor, 0, 4, ctx->stream)) return fail_hip(e2, "hipMemsetAsync", __LINE__);
         hipLaunchKernelGGL(k_gap_expand, dim3((v->nblocks + 3u) / 4u), dim3(256), 0, ctx->stream,
                            v->d_desc, v->nblocks, (u64*)p, (uint4*)(p + desc_bytes), cursor);
-        if (hipError_t e2 = hipGetLastError()) { cleanup(); return fail_hip(e2, "k_gap_expand", __LINE__); }
+        if (hipError_t e2 = hipGetLastError()) return fail_hip(e2, "k_gap_expand", __LINE__);
         expanded[v] = tab[e] = (u64)(uintptr_t)p;
     }
-    void* d_tab = nullptr;
-    if ((rc = dmalloc(ctx, &d_tab, tab.size() * 8)) || (rc = h2d_staged(ctx, d_tab, tab.data(), tab.size() * 8))) { dfree(ctx, d_tab); cleanup(); return rc; }
-    temps.push_back(d_tab);
-    const DmTab dt{(const u64*)d_tab, (u32)n, sym ? 0u : (u32)na};
+    bufs.emplace_back(ctx);
+    if ((rc = dmalloc(ctx, &bufs.back().p, tab.size() * 8)) || (rc = h2d_staged(ctx, bufs.back().p, tab.data(), tab.size() * 8))) return rc;
+    const DmTab dt{(const u64*)bufs.back(), (u32)n, sym ? 0u : (u32)na};
     if (d_and && ncols) {
         // tile pairs (ti | tj << 16; symmetric: ti <= tj) x column splits: enough workgroups for two per CU several times
         // over, a split never longer than 65,535 columns (the u32 counters of the tile kernel)
@@ -4144,14 +4112,14 @@ static int distance_matrix_launch(bmx_ctx* ctx, const bmx_vec* const* a, size_t 
         splits = std::max(splits, (ncols + 65534u) / 65535u);
         const u32 cps = (ncols + splits - 1u) / splits;
         splits = (ncols + cps - 1u) / cps;
-        void* d_pairs = nullptr;
-        if ((rc = dmalloc(ctx, &d_pairs, pairs.size() * 4)) || (rc = h2d_staged(ctx, d_pairs, pairs.data(), pairs.size() * 4))) { dfree(ctx, d_pairs); cleanup(); return rc; }
-        temps.push_back(d_pairs);
+        bufs.emplace_back(ctx);
+        if ((rc = dmalloc(ctx, &bufs.back().p, pairs.size() * 4)) || (rc = h2d_staged(ctx, bufs.back().p, pairs.data(), pairs.size() * 4))) return rc;
+        const u32* d_pairs = (const u32*)bufs.back();
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_distance_tile), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DM_LDS_BYTES);
-        if (e != hipSuccess) { cleanup(); return fail_hip(e, "hipFuncSetAttribute(k_distance_tile)", __LINE__); }
+        if (e != hipSuccess) return fail_hip(e, "hipFuncSetAttribute(k_distance_tile)", __LINE__);
         hipLaunchKernelGGL(k_distance_tile, dim3(np, splits), dim3(256), DM_LDS_BYTES, ctx->stream,
-                           dt, (u32)na, (u32)nb, (const u32*)d_pairs, cps, ncols, sym ? 1 : 0, (const u64*)ctx->d_zero, d_and);
-        if ((e = hipGetLastError()) != hipSuccess) { cleanup(); return fail_hip(e, "k_distance_tile", __LINE__); }
+                           dt, (u32)na, (u32)nb, d_pairs, cps, ncols, sym ? 1 : 0, (const u64*)ctx->d_zero, d_and);
+        if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "k_distance_tile", __LINE__);
     }
     if (d_ca || d_cb) {
         hipError_t e = hipSuccess;
@@ -4163,9 +4131,8 @@ static int distance_matrix_launch(bmx_ctx* ctx, const bmx_vec* const* a, size_t 
             if (d_cb) hipLaunchKernelGGL(k_distance_counts, dim3(gx, (u32)nb), dim3(256), 0, ctx->stream, dt, sym ? 0u : (u32)na, d_cb);
         }
         if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) { cleanup(); return fail_hip(e, "k_distance_counts", __LINE__); }
+        if (e != hipSuccess) return fail_hip(e, "k_distance_counts", __LINE__);
     }
-    cleanup();
     return BMX_OK;
 }
 
@@ -4210,14 +4177,15 @@ int bmx_distance_matrix(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const 
     if (!na || !nb) return BMX_OK;
     if ((rc = set_dev(ctx))) return rc;
     const size_t nn = na * nb;
-    u64* d = nullptr;
-    if ((rc = dmalloc(ctx, (void**)&d, (nn + na + nb) * 8))) return rc;
+    DevBuf buf(ctx);
+    if ((rc = dmalloc(ctx, &buf.p, (nn + na + nb) * 8))) return rc;
+    u64* d = (u64*)buf;
     std::vector<u64> h(nn + na + nb);
     rc = distance_matrix_launch(ctx, a, na, b, nb, d, d + nn, d + nn + na);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dfree(ctx, d);
+    buf.reset();
     if (rc) return rc;
     if (e != hipSuccess) return fail_hip(e, "bmx_distance_matrix", __LINE__);
     const u64* ca = h.data() + nn;

@@ -247,6 +247,69 @@ static int load_rccl(bmx_group* g, const int* devices)
     return BMX_OK;
 }
 
+// the only places where the group handles' members are freed; the status is the first a member's release reported
+static void group_release(bmx_group* g)
+{
+    workers_stop(g);
+    for (size_t m = 0; m < g->comm.size(); ++m) if (g->comm[m] && g->p_comm_destroy) (void)g->p_comm_destroy(g->comm[m]);
+    for (bmx_ctx* c : g->ctx) if (c) ctx_release(c);
+    // librccl stays loaded: unloading a library that registered HIP fat binaries is not safe
+    delete g;
+}
+static int gvec_release(bmx_gvec* v)
+{
+    int rc = BMX_OK;
+    for (bmx_vec* s : v->shard) if (s) { int r = vec_release(s); if (r && !rc) rc = r; }
+    delete v;
+    return rc;
+}
+
+static int grs_release(bmx_grs* rs)
+{
+    int rc = BMX_OK;
+    for (bmx_rs* r1 : rs->rs) if (r1) { int r = rs_release(r1); if (r && !rc) rc = r; }
+    delete rs;
+    return rc;
+}
+
+static int gpipeline_release(bmx_gpipeline* p)
+{
+    bmx_group* g = p->g;
+    for (int m = 0; m < g->n; ++m) {
+        bmx_ctx* c = g->ctx[(size_t)m];
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        if ((size_t)m < p->pipe.size() && p->pipe[(size_t)m]) (void)pipeline_release(p->pipe[(size_t)m]);
+        if ((size_t)m < p->d_counts.size() && p->d_counts[(size_t)m]) (void)hipFree(p->d_counts[(size_t)m]);
+        if ((size_t)m < p->ev0.size() && p->ev0[(size_t)m]) (void)hipEventDestroy(p->ev0[(size_t)m]);
+        if ((size_t)m < p->ev1.size() && p->ev1[(size_t)m]) (void)hipEventDestroy(p->ev1[(size_t)m]);
+        if ((size_t)m < p->ev2.size() && p->ev2[(size_t)m]) (void)hipEventDestroy(p->ev2[(size_t)m]);
+    }
+    if (p->h_counts) (void)hipHostFree(p->h_counts);
+    delete p;
+    return BMX_OK;
+}
+
+// The owner of a group handle while it is built: an error path releases it and keeps the text of the first error (a host exception
+// while freeing is dropped, as in Releaser)
+struct GroupReleaser {
+    template <class F> static void keep_error(F release) { try { std::string keep = bmx_last_error(); release(); bmx_set_last_error(keep.c_str()); } catch (...) {} }
+    void operator()(bmx_gvec* v) const { keep_error([v] { (void)gvec_release(v); }); }
+    void operator()(bmx_grs* rs) const { keep_error([rs] { (void)grs_release(rs); }); }
+    void operator()(bmx_gpipeline* p) const { keep_error([p] { (void)gpipeline_release(p); }); }
+    void operator()(bmx_group* g) const { keep_error([g] { group_release(g); }); }
+};
+template <class T> using GOwned = std::unique_ptr<T, GroupReleaser>;
+
+static GOwned<bmx_gvec> gvec_new(bmx_group* g, uint64_t nbits, uint32_t nblocks)
+{
+    GOwned<bmx_gvec> v(new bmx_gvec());
+    v->g = g; v->nbits = nbits; v->nblocks = nblocks;
+    v->part = part_for(g, nblocks);
+    v->shard.assign((size_t)g->n, nullptr);
+    return v;
+}
+
 extern "C" {
 
 int bmx_group_create(const int* devices, int n, int flags, bmx_group** out)
@@ -256,31 +319,17 @@ int bmx_group_create(const int* devices, int n, int flags, bmx_group** out)
     if (flags & BMX_GROUP_RCCL)
         for (int a = 0; a < n; ++a) for (int b = a + 1; b < n; ++b)
             if (devices[a] == devices[b]) { bmx_set_last_error("BMX_GROUP_RCCL needs distinct devices"); return BMX_ERR_BADARG; }
-    bmx_group* g = new (std::nothrow) bmx_group();
-    if (!g) return BMX_ERR_BADALLOC;
+    GOwned<bmx_group> g(new bmx_group());
     g->n = n; g->flags = flags;
-    for (int m = 0; m < n; ++m) {
-        bmx_ctx* c = nullptr;
-        int rc = bmx_ctx_create(devices[m], nullptr, &c);
-        if (rc) { bmx_group_destroy(g); return rc; }
-        g->ctx.push_back(c);
-    }
-    if (flags & BMX_GROUP_RCCL) { int rc = load_rccl(g, devices); if (rc) { bmx_group_destroy(g); return rc; } }
-    { int rc = workers_start(g); if (rc) { bmx_group_destroy(g); return rc; } }
-    *out = g;
+    g->ctx.assign((size_t)n, nullptr);
+    for (int m = 0; m < n; ++m) { int rc = bmx_ctx_create(devices[m], nullptr, &g->ctx[(size_t)m]); if (rc) return rc; }
+    if (flags & BMX_GROUP_RCCL) { int rc = load_rccl(g.get(), devices); if (rc) return rc; }
+    { int rc = workers_start(g.get()); if (rc) return rc; }
+    *out = g.release();
     return BMX_OK;
 ABI_END }
 
-int bmx_group_destroy(bmx_group* g)
-{ ABI_TRY
-    if (!g) return BMX_OK;
-    workers_stop(g);
-    for (size_t m = 0; m < g->comm.size(); ++m) if (g->comm[m] && g->p_comm_destroy) (void)g->p_comm_destroy(g->comm[m]);
-    for (bmx_ctx* c : g->ctx) bmx_ctx_destroy(c);
-    // librccl stays loaded: unloading a library that registered HIP fat binaries is not safe
-    delete g;
-    return BMX_OK;
-ABI_END }
+int bmx_group_destroy(bmx_group* g) { ABI_TRY if (g) group_release(g); return BMX_OK; ABI_END }
 
 int bmx_group_size(const bmx_group* g, int* n) { ABI_TRY ARGCHK(g && n); *n = g->n; return BMX_OK; ABI_END }
 
@@ -379,25 +428,7 @@ int bmx_group_rccl_ranks(const bmx_group* g, int* n)
     return BMX_OK;
 ABI_END }
 
-static bmx_gvec* gvec_new(bmx_group* g, uint64_t nbits, uint32_t nblocks)
-{
-    bmx_gvec* v = new (std::nothrow) bmx_gvec();
-    if (!v) return nullptr;
-    v->g = g; v->nbits = nbits; v->nblocks = nblocks;
-    v->part = part_for(g, nblocks);
-    v->shard.assign((size_t)g->n, nullptr);
-    return v;
-}
-
-int bmx_gvec_free(bmx_group* g, bmx_gvec* v)
-{ ABI_TRY
-    if (!v) return BMX_OK;
-    ARGCHK(g && v->g == g);
-    int rc = BMX_OK;
-    for (int m = 0; m < g->n; ++m) { int r = bmx_vec_free(g->ctx[(size_t)m], v->shard[(size_t)m]); if (r && !rc) rc = r; }
-    delete v;
-    return rc;
-ABI_END }
+int bmx_gvec_free(bmx_group* g, bmx_gvec* v) { ABI_TRY if (!v) return BMX_OK; ARGCHK(g && v->g == g); return gvec_release(v); ABI_END }
 
 static uint64_t shard_bits(uint64_t nbits, uint32_t lo, uint32_t hi)
 {
@@ -411,10 +442,9 @@ int bmx_gvec_upload(bmx_group* g, uint64_t nbits, uint32_t nblocks, const uint8_
 { ABI_TRY
     ARGCHK(g && out && (nblocks == 0 || (kinds && offs)));
     *out = nullptr;
-    bmx_gvec* v = gvec_new(g, nbits, nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gvec> v = gvec_new(g, nbits, nblocks);
     int rc = for_each_member(g, [&](int m) -> int {
-        uint32_t lo, hi; shard_of(v, m, &lo, &hi);
+        uint32_t lo, hi; shard_of(v.get(), m, &lo, &hi);
         // the piece of each slab this shard references: [min offset, max end) -- exact for tables in block
         // order (what a tree walk or a frozen arena yields), still correct for any other order
         uint32_t bmin = 0xFFFFFFFFu, bmax = 0; uint64_t gmin = ~0ull, gmax = 0;
@@ -437,8 +467,8 @@ int bmx_gvec_upload(bmx_group* g, uint64_t nbits, uint32_t nblocks, const uint8_
                               bmax > bmin ? bit_slab + (size_t)bmin * BMX_BLOCK_WORDS : nullptr, bmax - bmin,
                               gmax > gmin ? gap_slab + gmin : nullptr, gmax - gmin, &v->shard[(size_t)m]);
     });
-    if (rc) { std::string keep = bmx_last_error(); bmx_gvec_free(g, v); bmx_set_last_error(keep.c_str()); return rc; }
-    *out = v;
+    if (rc) return rc;
+    *out = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -449,15 +479,14 @@ int bmx_gvec_generate(bmx_group* g, uint64_t seed, uint32_t vec_id, int with_com
     *out = nullptr;
     uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
     if (nblocks64 > 65536ull * 16) { bmx_set_last_error("vector too long"); return BMX_ERR_RANGE; }
-    bmx_gvec* v = gvec_new(g, nbits, (uint32_t)nblocks64);
-    if (!v) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gvec> v = gvec_new(g, nbits, (uint32_t)nblocks64);
     int rc = for_each_member(g, [&](int m) -> int {
-        uint32_t lo, hi; shard_of(v, m, &lo, &hi);
+        uint32_t lo, hi; shard_of(v.get(), m, &lo, &hi);
         return bmx_vec_generate_shard(g->ctx[(size_t)m], seed, vec_id, with_common, density_q16, nbits, lo, hi, optimize,
                                       &v->shard[(size_t)m]);
     });
-    if (rc) { std::string keep = bmx_last_error(); bmx_gvec_free(g, v); bmx_set_last_error(keep.c_str()); return rc; }
-    *out = v;
+    if (rc) return rc;
+    *out = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -547,34 +576,24 @@ int bmx_gvec_op2(bmx_group* g, int op, const bmx_gvec* a, const bmx_gvec* b, int
     ARGCHK(g && a && b && result && a->g == g && b->g == g);
     *result = nullptr;
     if (a->nblocks != b->nblocks || a->part != b->part) { bmx_set_last_error("sharded operands must cover the same block range (upload them with the same nblocks)"); return BMX_ERR_BADARG; }
-    bmx_gvec* v = gvec_new(g, std::max(a->nbits, b->nbits), a->nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gvec> v = gvec_new(g, std::max(a->nbits, b->nbits), a->nblocks);
     int rc = for_each_member(g, [&](int m) -> int {
         return bmx_op2(g->ctx[(size_t)m], op, a->shard[(size_t)m], b->shard[(size_t)m], opt_compress, &v->shard[(size_t)m]);
     });
-    if (rc) { std::string keep = bmx_last_error(); bmx_gvec_free(g, v); bmx_set_last_error(keep.c_str()); return rc; }
-    *result = v;
+    if (rc) return rc;
+    *result = v.release();
     return BMX_OK;
 ABI_END }
 
 // ---- rank / select over a sharded vector (per-shard index, one exchange of the shard totals,
 // queries routed to the shard that owns the block) ----
-int bmx_grs_free(bmx_group* g, bmx_grs* rs)
-{ ABI_TRY
-    if (!rs) return BMX_OK;
-    ARGCHK(g && rs->g == g);
-    int rc = BMX_OK;
-    for (int m = 0; m < g->n; ++m) { int r = bmx_rs_free(g->ctx[(size_t)m], rs->rs[(size_t)m]); if (r && !rc) rc = r; }
-    delete rs;
-    return rc;
-ABI_END }
+int bmx_grs_free(bmx_group* g, bmx_grs* rs) { ABI_TRY if (!rs) return BMX_OK; ARGCHK(g && rs->g == g); return grs_release(rs); ABI_END }
 
 int bmx_grs_build(bmx_group* g, const bmx_gvec* v, bmx_grs** out)
 { ABI_TRY
     ARGCHK(g && v && out && v->g == g);
     *out = nullptr;
-    bmx_grs* rs = new (std::nothrow) bmx_grs();
-    if (!rs) return BMX_ERR_BADALLOC;
+    GOwned<bmx_grs> rs(new bmx_grs());
     rs->g = g; rs->v = v;
     rs->rs.assign((size_t)g->n, nullptr);
     int rc = for_each_member(g, [&](int m) -> int { return bmx_rs_build(g->ctx[(size_t)m], v->shard[(size_t)m], &rs->rs[(size_t)m]); });
@@ -584,8 +603,8 @@ int bmx_grs_build(bmx_group* g, const bmx_gvec* v, bmx_grs** out)
         rc = bmx_rs_count(rs->rs[(size_t)m], &c);
         rs->before[(size_t)m + 1] = rs->before[(size_t)m] + c;
     }
-    if (rc) { std::string keep = bmx_last_error(); bmx_grs_free(g, rs); bmx_set_last_error(keep.c_str()); return rc; }
-    *out = rs;
+    if (rc) return rc;
+    *out = rs.release();
     return BMX_OK;
 ABI_END }
 
@@ -695,15 +714,14 @@ int bmx_gagg_or(bmx_group* g, const bmx_gvec* const* src, size_t n, int opt_comp
     uint32_t nblocks = 0xFFFFFFFFu; uint64_t nbits = 0;
     int rc = same_range(g, src, n, &nblocks, &nbits); if (rc) return rc;
     if (nblocks == 0xFFFFFFFFu) nblocks = 0;
-    bmx_gvec* v = gvec_new(g, nbits, nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gvec> v = gvec_new(g, nbits, nblocks);
     rc = for_each_member(g, [&](int m) -> int {
         std::vector<const bmx_vec*> h(std::max<size_t>(n, 1));
         for (size_t i = 0; i < n; ++i) h[i] = src[i]->shard[(size_t)m];
         return bmx_agg_or_opt(g->ctx[(size_t)m], h.data(), n, opt_compress, &v->shard[(size_t)m]);
     });
-    if (rc) { std::string keep = bmx_last_error(); bmx_gvec_free(g, v); bmx_set_last_error(keep.c_str()); return rc; }
-    *result = v;
+    if (rc) return rc;
+    *result = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -717,8 +735,7 @@ int bmx_gagg_and_sub(bmx_group* g, const bmx_gvec* const* src_and, size_t n_and,
     int rc = same_range(g, src_and, n_and, &nblocks, &nbits); if (rc) return rc;
     rc = same_range(g, src_sub, n_sub, &nblocks, &nbits); if (rc) return rc;
     if (nblocks == 0xFFFFFFFFu) nblocks = 0;
-    bmx_gvec* v = gvec_new(g, nbits, nblocks);
-    if (!v) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gvec> v = gvec_new(g, nbits, nblocks);
     std::vector<int> many((size_t)g->n, 0);
     rc = for_each_member(g, [&](int m) -> int {
         std::vector<const bmx_vec*> a(std::max<size_t>(n_and, 1)), s(std::max<size_t>(n_sub, 1));
@@ -726,9 +743,9 @@ int bmx_gagg_and_sub(bmx_group* g, const bmx_gvec* const* src_and, size_t n_and,
         for (size_t i = 0; i < n_sub; ++i) s[i] = src_sub[i]->shard[(size_t)m];
         return bmx_agg_and_sub(g->ctx[(size_t)m], a.data(), n_and, s.data(), n_sub, &v->shard[(size_t)m], &many[(size_t)m]);
     });
-    if (rc) { std::string keep = bmx_last_error(); bmx_gvec_free(g, v); bmx_set_last_error(keep.c_str()); return rc; }
+    if (rc) return rc;
     if (any) for (int m = 0; m < g->n; ++m) *any |= many[(size_t)m];
-    *result = v;
+    *result = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -782,8 +799,7 @@ int bmx_gslice_compare(bmx_group* g, const bmx_gvec* const* slices, size_t nslic
     if (need != nblocks || (not_null && (not_null->g != g || not_null->nblocks != nblocks))) {
         bmx_set_last_error("size / not-NULL vector must span the block range of the planes"); return BMX_ERR_BADARG;
     }
-    bmx_gvec* v = result ? gvec_new(g, size, nblocks) : nullptr;
-    if (result && !v) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gvec> v = result ? gvec_new(g, size, nblocks) : nullptr;
     part_ref pr = part_for(g, nblocks);
     std::vector<uint64_t> cnt((size_t)g->n, 0);
     int rc = for_each_member(g, [&](int m) -> int {
@@ -794,9 +810,9 @@ int bmx_gslice_compare(bmx_group* g, const bmx_gvec* const* slices, size_t nslic
                                  not_null ? not_null->shard[(size_t)m] : nullptr, v ? &v->shard[(size_t)m] : nullptr,
                                  count ? &cnt[(size_t)m] : nullptr);
     });
-    if (rc) { std::string keep = bmx_last_error(); if (v) bmx_gvec_free(g, v); bmx_set_last_error(keep.c_str()); return rc; }
+    if (rc) return rc;
     if (count) for (int m = 0; m < g->n; ++m) *count += cnt[(size_t)m];
-    if (result) *result = v;
+    if (result) *result = v.release();
     return BMX_OK;
 ABI_END }
 
@@ -832,24 +848,7 @@ int bmx_gslice_eq_counts(bmx_group* g, const bmx_gvec* const* slices, size_t nsl
     return BMX_OK;
 ABI_END }
 
-int bmx_gpipeline_destroy(bmx_group* g, bmx_gpipeline* p)
-{ ABI_TRY
-    if (!p) return BMX_OK;
-    ARGCHK(g && p->g == g);
-    for (int m = 0; m < g->n; ++m) {
-        bmx_ctx* c = g->ctx[(size_t)m];
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        if ((size_t)m < p->pipe.size()) bmx_pipeline_destroy(c, p->pipe[(size_t)m]);
-        if ((size_t)m < p->d_counts.size() && p->d_counts[(size_t)m]) (void)hipFree(p->d_counts[(size_t)m]);
-        if ((size_t)m < p->ev0.size() && p->ev0[(size_t)m]) (void)hipEventDestroy(p->ev0[(size_t)m]);
-        if ((size_t)m < p->ev1.size() && p->ev1[(size_t)m]) (void)hipEventDestroy(p->ev1[(size_t)m]);
-        if ((size_t)m < p->ev2.size() && p->ev2[(size_t)m]) (void)hipEventDestroy(p->ev2[(size_t)m]);
-    }
-    if (p->h_counts) (void)hipHostFree(p->h_counts);
-    delete p;
-    return BMX_OK;
-ABI_END }
+int bmx_gpipeline_destroy(bmx_group* g, bmx_gpipeline* p) { ABI_TRY if (!p) return BMX_OK; ARGCHK(g && p->g == g); return gpipeline_release(p); ABI_END }
 
 int bmx_gpipeline_create(bmx_group* g, const bmx_gvec* const* and_list, const uint32_t* and_n,
                          const bmx_gvec* const* sub_list, const uint32_t* sub_n, size_t ngroups, bmx_gpipeline** out)
@@ -863,8 +862,7 @@ int bmx_gpipeline_create(bmx_group* g, const bmx_gvec* const* and_list, const ui
     uint32_t nblocks = 0xFFFFFFFFu; uint64_t nbits = 0;
     int rc = same_range(g, and_list, tot_and, &nblocks, &nbits); if (rc) return rc;
     rc = same_range(g, sub_list, tot_sub, &nblocks, &nbits); if (rc) return rc;
-    bmx_gpipeline* p = new (std::nothrow) bmx_gpipeline();
-    if (!p) return BMX_ERR_BADALLOC;
+    GOwned<bmx_gpipeline> p(new bmx_gpipeline());
     p->g = g; p->ngroups = (uint32_t)ngroups;
     p->pipe.assign((size_t)g->n, nullptr); p->d_counts.assign((size_t)g->n, nullptr);
     p->ev0.assign((size_t)g->n, nullptr); p->ev1.assign((size_t)g->n, nullptr); p->ev2.assign((size_t)g->n, nullptr);
@@ -887,8 +885,8 @@ int bmx_gpipeline_create(bmx_group* g, const bmx_gvec* const* and_list, const ui
         hipError_t e = hipHostMalloc((void**)&p->h_counts, (size_t)g->n * ngroups * 8);
         if (e != hipSuccess) rc = bmx_fail_hip(e, "hipHostMalloc", __FILE__, __LINE__);
     }
-    if (rc) { std::string keep = bmx_last_error(); bmx_gpipeline_destroy(g, p); bmx_set_last_error(keep.c_str()); return rc; }
-    *out = p;
+    if (rc) return rc;
+    *out = p.release();
     return BMX_OK;
 ABI_END }
 

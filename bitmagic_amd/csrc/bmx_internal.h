@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <map>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -23,12 +24,17 @@ void bmx_set_last_error(const char* msg);
 #define ARGCHK(cond) do { if (!(cond)) { bmx_set_last_error("bad argument: " #cond); return BMX_ERR_BADARG; } } while (0)
 #define KCHK() HIPCHK(hipGetLastError())
 #define PEND_SLOTS 1024
-// the exception barrier around every extern "C" body: { ABI_TRY ... ABI_END }  (bmx.hip: bmx_abi_caught)
+// the exception barrier around every extern "C" body: { ABI_TRY ... ABI_END }  (bmx.hip: bmx_abi_caught).  AbiDepth counts the
+// barriers this thread is inside (an exception unwinds it too): only an outermost entry takes a step of the injection countdown
+// (bmx_abi_enter); ABI_TRY_UNCOUNTED is the barrier of bmx_debug_inject_failure, which never does
 #include <new>
 #include <stdexcept>
 int bmx_abi_caught(int kind, const char* what);
 void bmx_abi_enter();
-#define ABI_TRY try { bmx_abi_enter();
+extern thread_local int bmx_abi_depth;
+struct AbiDepth { AbiDepth() { ++bmx_abi_depth; } ~AbiDepth() { --bmx_abi_depth; } };
+#define ABI_TRY_UNCOUNTED try { AbiDepth abi_depth_;
+#define ABI_TRY ABI_TRY_UNCOUNTED bmx_abi_enter();
 #define ABI_END } catch (const std::bad_alloc&) { return bmx_abi_caught(0, nullptr); } catch (const std::exception& e_) { return bmx_abi_caught(1, e_.what()); } catch (...) { return bmx_abi_caught(2, nullptr); }
 
 struct bmx_ctx {
@@ -64,6 +70,7 @@ struct bmx_ctx {
     std::unordered_map<void*, RzInfo> rz_live;               // user pointer -> what lies around it
     uint64_t rz_hits = 0; std::string rz_report;             // allocations found damaged so far, and where they came from
     long long fail_dmalloc_after = -1;                        // debug fault injection: the allocation this many dmallocs from now fails (bmx_debug_inject_failure kind 4)
+    bool fail_dmalloc_throws = false;                         // ... by throwing std::bad_alloc (kind 6)
     int pipe_unroll = 0;       // operand slices per batch (two batches in flight); 0 = the measured best for the slice size
     int pipe_rows = 0;         // register rows (KiB of a block) per work item: 8 = whole block, 4/2/1 = slices, 0 = auto by item count
     int pipe_nt = 1;           // non-temporal operand loads (+4.5 % on the streamed-once headline case)
@@ -121,43 +128,44 @@ struct bmx_ctx {
 };
 
 struct bmx_vec {
-    bmx_ctx* ctx;
-    uint64_t uid;                                             // never reused: keys of the packed-collection cache
-    uint64_t nbits; uint32_t nblocks;
-    uint32_t counts[4]; uint64_t gap_words; uint32_t n_bit;   // n_bit = slots of d_bits
-    u64* d_desc; uint4* d_bits; u16* d_gaps;
-    u32* d_ord;        // result vectors whose slab has unused slots: ordinal of every bit-block (download gathers), else null
-    bool ord_lazy;     // ... whose ordinals have not been computed yet (vec_build_ord does it when a download first needs them)
-    void* d_tdir;      // tile directory (bmx_kernels7.h): 16 B per 14 blocks, vectors with GAP or FULL blocks only, else null
-    uint64_t count; bool count_valid;                         // popcount of the vector when the kernel that produced it folded one
-    size_t bytes;
+    bmx_ctx* ctx = nullptr;
+    uint64_t uid = 0;                                         // never reused: keys of the packed-collection cache
+    uint64_t nbits = 0; uint32_t nblocks = 0;
+    uint32_t counts[4] = {}; uint64_t gap_words = 0; uint32_t n_bit = 0;   // n_bit = slots of d_bits
+    u64* d_desc = nullptr; uint4* d_bits = nullptr; u16* d_gaps = nullptr;
+    u32* d_ord = nullptr;      // result vectors whose slab has unused slots: ordinal of every bit-block (download gathers), else null
+    bool ord_lazy = false;     // ... whose ordinals have not been computed yet (vec_build_ord does it when a download first needs them)
+    void* d_tdir = nullptr;    // tile directory (bmx_kernels7.h): 16 B per 14 blocks, vectors with GAP or FULL blocks only, else null
+    uint64_t count = 0; bool count_valid = false;             // popcount of the vector when the kernel that produced it folded one
+    size_t bytes = 0;
 };
 
 struct bmx_pipeline {
-    bmx_ctx* ctx;
-    uint32_t ngroups, ncols, col_stride, n_ops;
-    uint32_t null_row_off;                // every column record ends with a row that is always ROW_EMPTY: what the asynchronous counts run under a search limit points a finished group at
-    bool has_gap;
+    bmx_ctx* ctx = nullptr;
+    uint32_t ngroups = 0, ncols = 0, col_stride = 0, n_ops = 0;
+    uint32_t null_row_off = 0;            // every column record ends with a row that is always ROW_EMPTY: what the asynchronous counts run under a search limit points a finished group at
+    bool has_gap = false;
     bool has_bit = false;      // any operand vector holds a bit-block
     uint32_t gap_avg_words = 0;  // average GAP block size of the operands (16-bit words incl. padding)
-    uint64_t nbits;                       // max size of the operands
+    uint64_t nbits = 0;                   // max size of the operands
     // LDS-staged path (k_pipe_counts_staged): distinct vectors ("planes") + per-group plane masks
-    uint32_t nplanes, nchunks; bool staged_ok;
-    const u64** d_udesc; u32* d_unblk; u32* d_gmask; u32* d_gskip;
-    std::vector<u32>* h_row_off;          // host copy: row offset of each group inside a column record
-    std::vector<u32>* h_and_n;            // host copy: AND operands per group
-    std::vector<u32>* h_sub_n = nullptr;  // host copy: SUB operands per group
-    u64* d_dmat;
-    u32* d_meta;       // row_off | and_n | sub_n | and_off | sub_off (ngroups each) | nblocks (n_ops)
-    const u64** d_descs;
-    size_t bytes;
-    // GAP-only pipelines: the uids of the operand vectors (AND lists, then SUB lists, in group order) -- never the pointers: a
-    // vector freed before the pipeline is simply not found in any collection any more -- and what they resolved to
+    uint32_t nplanes = 0, nchunks = 0; bool staged_ok = false;
+    const u64** d_udesc = nullptr; u32* d_unblk = nullptr; u32* d_gmask = nullptr; u32* d_gskip = nullptr;
+    std::vector<u32> h_row_off;           // host copy: row offset of each group inside a column record
+    std::vector<u32> h_and_n;             // host copy: AND operands per group
+    std::vector<u32> h_sub_n;             // host copy: SUB operands per group
+    u64* d_dmat = nullptr;
+    u32* d_meta = nullptr;     // row_off | and_n | sub_n | and_off | sub_off (ngroups each) | nblocks (n_ops)
+    const u64** d_descs = nullptr;
+    size_t bytes = 0;
     uint64_t search_limit = ~0ull;       // pipeline::set_search_count_limit (src/bmaggregator.h:255): a group needs no more than this many hits
     uint32_t last_windows = 0, last_windows_planned = 0;   // launch windows of the last synchronous counts run under a limit
-    std::vector<uint32_t>* h_win_groups = nullptr;        // ... and the arg-groups every launched window ran over
-    std::vector<uint32_t>* h_stop = nullptr;              // ... and, per group, the block column at which it reached the limit (0xFFFFFFFF: never)
-    std::vector<uint64_t>* h_uids = nullptr;
+    std::vector<uint32_t> h_win_groups;                   // ... and the arg-groups every launched window ran over
+    std::vector<uint32_t> h_stop;                         // ... and, per group, the block column at which it reached the limit (0xFFFFFFFF: never)
+    // GAP-only pipelines: the uids of the operand vectors (AND lists, then SUB lists, in group order) -- never the pointers: a
+    // vector freed before the pipeline is simply not found in any collection any more -- and what they resolved to.  Non-empty
+    // exactly for "GAP-only pipelines" (AND operands, no bit-block)
+    std::vector<uint64_t> h_uids;
     uint64_t cm_gen = ~0ull;            // ctx->coll_gen at the last resolution
     uint64_t cm_tried_gen = ~0ull - 1;  // ctx->coll_gen after the last attempt to build the group's collections (gap_pack 1): not retried until it changes
     uint64_t cm_a_id = 0, cm_s_id = 0;  // collections serving the AND lists / SUB lists (0 = none)
@@ -169,47 +177,65 @@ struct bmx_pipeline {
 // a column-major packed interval collection of a set of vectors (bmx_kernels6.h) with its member directory (bmx_kernels8.h)
 struct bmx_coll {
     std::vector<uint64_t> key;            // member uids in member order
-    std::unordered_map<uint64_t, uint32_t>* index;   // uid -> member index
-    int polarity;
-    uint32_t ncols, nvec;
-    u32* d_runs; u64* d_off; u32* d_cnt; u32* d_flags;
-    u32* d_cnt_s;                         // split bag (polarity 1): single-bit runs per column, kept as 16-bit positions behind the multi-bit runs; else null
-    u32* d_dir; u32* d_dir_s;             // member directory [ncols][nvec + 1]: entries (split: multi-bit runs) before member i | kind << 30; singles before member i
+    std::unordered_map<uint64_t, uint32_t> index;   // uid -> member index
+    int polarity = 0;
+    uint32_t ncols = 0, nvec = 0;
+    u32* d_runs = nullptr; u64* d_off = nullptr; u32* d_cnt = nullptr; u32* d_flags = nullptr;
+    u32* d_cnt_s = nullptr;               // split bag (polarity 1): single-bit runs per column, kept as 16-bit positions behind the multi-bit runs; else null
+    u32* d_dir = nullptr; u32* d_dir_s = nullptr;   // member directory [ncols][nvec + 1]: entries (split: multi-bit runs) before member i | kind << 30; singles before member i
     u32* d_bt = nullptr;                  // tile build (bmx_kernels10.h): the (tile, group of 64 members, column) run counts, kept so that the
     bool dir_pending = false;             // ... member directory can be built when a call first needs it (coll_ensure_dir)
-    uint64_t entries, bytes, run_bytes, last_use, id;
-    uint64_t alg_bytes;                   // algorithmic bytes of the GAP operands: sum of 2 x (len + 1)
-    bool has_bit;                         // a bit-block was found while counting: unusable
-    bool prepared;                        // built by bmx_collection_prepare (not by the gap_pack 1 policy)
+    uint64_t entries = 0, bytes = 0, run_bytes = 0, last_use = 0, id = 0;
+    uint64_t alg_bytes = 0;               // algorithmic bytes of the GAP operands: sum of 2 x (len + 1)
+    bool has_bit = false;                 // a bit-block was found while counting: unusable
+    bool prepared = false;                // built by bmx_collection_prepare (not by the gap_pack 1 policy)
     int pins = 0;                         // > 0 while a one-shot call holds a raw pointer to it across allocations: never evicted then
-    float build_ms;
+    float build_ms = 0.f;
 };
 
 // an asynchronous result (bmx_op2_dev): the vector is complete on the stream, its block-kind counts are on their way into a
 // pinned slot; bmx_pending_wait turns it into an ordinary vector.  A handle type of its own: no other entry can be handed one.
 struct bmx_pending {
-    bmx_ctx* ctx;
-    bmx_vec* v;
-    int slot;
-    hipEvent_t ev;
-    uint64_t gap_bound;       // upper bound of the GAP words the result holds (0: it cannot hold a GAP block); its GAP slab has that size
-    void* scratch;            // st[] / offs[] / candidate list of the producing kernel (GAP path), until the result is resolved
-    bool resolved;            // the vector is already an ordinary one (x & x, x | x: a block-for-block copy): the wait only hands it over
+    bmx_ctx* ctx = nullptr;
+    bmx_vec* v = nullptr;
+    int slot = -1;
+    hipEvent_t ev = nullptr;
+    uint64_t gap_bound = 0;   // upper bound of the GAP words the result holds (0: it cannot hold a GAP block); its GAP slab has that size
+    void* scratch = nullptr;  // st[] / offs[] / candidate list of the producing kernel (GAP path), until the result is resolved
+    bool resolved = false;    // the vector is already an ordinary one (x & x, x | x: a block-for-block copy): the wait only hands it over
 };
 
 struct bmx_rs {
-    bmx_ctx* ctx;
-    uint32_t nblocks; uint64_t count;
-    u32* d_bcount; u64* d_sub; u64* d_rcount; u16* d_cum;
-    u16* d_gidx;                                          // GAP blocks: first run reaching each 1024-bit wave
-    u64* d_sample; uint32_t nsamples, sample_shift;       // top level of the select search (<= 2048 entries)
-    u32* d_lines;                                         // rank lines: 69 x 128 B per block (count before the line + 960 bits), or null
-    u32* d_sdir; uint32_t sdir_shift; uint64_t sdir_entries;  // with rank lines: select directory (line of every 2^shift-th one) + sentinel
-    u16* d_dir8;                                          // with rank lines: ones of a block before each of its eight 8,192-bit octants
+    bmx_ctx* ctx = nullptr;
+    uint32_t nblocks = 0; uint64_t count = 0;
+    u32* d_bcount = nullptr; u64* d_sub = nullptr; u64* d_rcount = nullptr; u16* d_cum = nullptr;
+    u16* d_gidx = nullptr;                                // GAP blocks: first run reaching each 1024-bit wave
+    u64* d_sample = nullptr; uint32_t nsamples = 0, sample_shift = 0;   // top level of the select search (<= 2048 entries)
+    u32* d_lines = nullptr;                               // rank lines: 69 x 128 B per block (count before the line + 960 bits), or null
+    u32* d_sdir = nullptr; uint32_t sdir_shift = 0; uint64_t sdir_entries = 0;  // with rank lines: select directory (line of every 2^shift-th one) + sentinel
+    u16* d_dir8 = nullptr;                                // with rank lines: ones of a block before each of its eight 8,192-bit octants
     u8* d_sel = nullptr; uint32_t sel_bits = 0; uint64_t sel_lines = 0;  // select lines (bmx_kernels11.h): the positions of the ones, K = 60 (16-bit offsets) / 30 (32-bit) per 128-byte line, or null
     u32* d_stop = nullptr; uint32_t stop_shift = 0, stop_fb = 0;       // with the select directory: its 65,536-entry summary for LDS (k_select_top): positions to 1 / 2^stop_fb of a line as base[1024] + 16-bit offsets, or null
-    size_t bytes;
+    size_t bytes = 0;
 };
+
+// The only places where a handle's members are freed (bmx.hip): the public free / destroy entries check their arguments and call
+// these.  vec / rs / pipeline: set the device, wait for the stream, return that status (the handle goes either way); pending_release
+// does not wait for the event.  A handle being built lives in an Owned<T>, handed out with `*out = h.release()`.  The deleters run
+// in destructors: a host exception while freeing (std::bad_alloc) is dropped there -- what it left leaks -- not std::terminate.
+int vec_release(bmx_vec* v);
+int rs_release(bmx_rs* rs);
+int pipeline_release(bmx_pipeline* p);
+int pending_release(bmx_pending* p);
+void ctx_release(bmx_ctx* ctx);
+struct Releaser {
+    void operator()(bmx_vec* v) const { try { (void)vec_release(v); } catch (...) {} }
+    void operator()(bmx_rs* rs) const { try { (void)rs_release(rs); } catch (...) {} }
+    void operator()(bmx_pipeline* p) const { try { (void)pipeline_release(p); } catch (...) {} }
+    void operator()(bmx_pending* p) const { try { (void)pending_release(p); } catch (...) {} }
+    void operator()(bmx_ctx* ctx) const { try { ctx_release(ctx); } catch (...) {} }
+};
+template <class T> using Owned = std::unique_ptr<T, Releaser>;
 
 // asynchronous building blocks the group layer composes (bmx.hip): everything is enqueued on ctx->stream,
 // the 8-byte results land in ctx->h_small[slot] (pinned) after the stream has been synchronised

@@ -523,9 +523,11 @@ int bmx_gpipeline_describe(bmx_group* g, bmx_gpipeline* p, int member, char* buf
 int bmx_debug_redzone_check(bmx_ctx* ctx, int* enabled, uint64_t* hits, char* report, size_t report_len);
 /* Fault injection for tests of the error paths.  kind 1 | 2 | 3: the library entry `after` calls from now on this thread throws
  * std::bad_alloc | std::length_error | a non-standard exception at its first statement -- what must come back is a status
- * (BMX_ERR_BADALLOC | BMX_ERR_DEVICE | BMX_ERR_DEVICE), never an exception (libbm.cpp:28-35); ctx may be NULL.  kind 4: the
- * device allocation `after` allocations from now on ctx fails with BMX_ERR_BADALLOC.  kind 5 (red-zone contexts): writes one byte
- * behind a fresh allocation -- the checker's self-test.  kind 0: disarm. */
+ * (BMX_ERR_BADALLOC | BMX_ERR_DEVICE | BMX_ERR_DEVICE), never an exception (libbm.cpp:28-35); ctx may be NULL.  Only entries
+ * made from outside the library count (an entry point another one calls does not); this call itself never counts.  kind 4: the
+ * device allocation `after` allocations from now on ctx fails with BMX_ERR_BADALLOC.  kind 6: the same allocation throws
+ * std::bad_alloc inside the library instead; the entry's barrier turns it into BMX_ERR_BADALLOC.  kind 5 (red-zone contexts):
+ * writes one byte behind a fresh allocation -- the checker's self-test.  kind 0: disarm. */
 int bmx_debug_inject_failure(bmx_ctx* ctx, int kind, long long after);
 
 /* ---- timing helper: HIP events on the context's stream ---- */

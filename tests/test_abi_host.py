@@ -193,6 +193,29 @@ def test_no_exception_crosses_the_abi():
     for _ in range(8): assert upload() == _ffi.ERR_BADARG
 
 
+def test_injection_counts_only_the_callers_entries():
+    """`after` counts the entries the caller makes: an entry point that calls another one (bmx_vec_generate ->
+    bmx_vec_generate_shard) takes one step, and bmx_debug_inject_failure itself takes none -- disarming an injection that is due at
+    the next entry returns OK and leaves nothing armed"""
+    from bitmagic_amd import _ffi
+    L = _ffi.lib()
+    null = C.c_void_p()
+    out = C.c_void_p()
+    def generate():                                     # BADARG on any machine (null context), through the nested entry
+        return L.bmx_vec_generate(null, 1, 0, 0, 655, 65536, 0, C.byref(out))
+    assert L.bmx_debug_inject_failure(null, 1, 1) == 0
+    assert generate() == _ffi.ERR_BADARG                # one step, not two
+    assert generate() == _ffi.ERR_BADALLOC and b"bad_alloc" in L.bmx_last_error()
+    assert generate() == _ffi.ERR_BADARG
+    assert L.bmx_debug_inject_failure(null, 1, 0) == 0
+    assert L.bmx_debug_inject_failure(null, 0, 0) == 0  # the disarm is not the entry that throws
+    assert generate() == _ffi.ERR_BADARG
+    n = C.c_int32()
+    assert L.bmx_group_size(null, C.byref(n)) == _ffi.ERR_BADARG
+    # kind 6 arms the device-allocation countdown of a context: it needs one
+    assert L.bmx_debug_inject_failure(null, 6, 0) == _ffi.ERR_BADARG
+
+
 def test_every_abi_body_sits_in_the_barrier():
     """each `int bmx_*` that include/bmx.h declares is defined with ABI_TRY ... ABI_END in bmx.hip / bmx_group.hip"""
     hdr = open(os.path.join(ROOT, "include", "bmx.h")).read()

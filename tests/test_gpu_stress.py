@@ -388,9 +388,11 @@ def test_red_zone_allocator_catches_overruns_and_the_suite_is_clean():
 
 
 def test_device_allocation_failures_come_back_as_status(port):
-    """fault injection (bmx_debug_inject_failure kind 4): the k-th device allocation of a call fails.  Whatever k, the call
-    returns BMX_ERR_BADALLOC (or succeeds, if it allocates fewer than k + 1 times) -- never a crash, never a wrong answer -- the
-    context keeps working, and what the failed call had allocated is given back."""
+    """fault injection (bmx_debug_inject_failure kind 4): the k-th device allocation of a call fails; kind 6: it throws
+    std::bad_alloc inside the library instead.  Whatever k, the call returns BMX_ERR_BADALLOC (or succeeds, if it allocates fewer
+    than k + 1 times) -- never a crash, never a wrong answer -- the context keeps working, and what the failed call had allocated
+    is given back."""
+    import torch
     c = bm.context(0)
     nbits = 30 * 65536 - 5
     vs = [bm.bvector.generate(c, 5, i, dq, nbits) for i, dq in enumerate((6554, 655, 66, 66, 200, 66))]
@@ -404,30 +406,88 @@ def test_device_allocation_failures_come_back_as_status(port):
         rs = vs[0].build_rs_index()
         return rs.count() == pv[0].count() and (vs[0].select(np.array([1, 77], np.uint64), rs)[1] == port.rs_build(pv[0]).select(np.array([1, 77], np.uint64))[0]).all()
     def prepare(): c.collection_prepare(vs[2:], 1); return agg.combine_or(vs[2:]).count() == exp_or
-    def pipeline():
+    def make_pipe(groups):
         pipe = bm.aggregator.pipeline(c)
-        ag = pipe.add(); ag.add(vs[0], 0); ag.add(vs[1], 0); ag.add(vs[4], 1)
-        pipe.complete()
-        return int(agg.combine_and_sub(pipe)[0]) == int(port.pipeline_counts([([pv[0], pv[1]], [pv[4]])])[0])
-    for name, fn in (("pairwise", pairwise), ("combine_or", combine_or), ("rs_index", rs_index), ("prepare", prepare), ("pipeline", pipeline)):
+        for a, s in groups:
+            ag = pipe.add()
+            for i in a: ag.add(vs[i], 0)
+            for i in s: ag.add(vs[i], 1)
+        return pipe
+    def expect(groups): return [int(x) for x in port.pipeline_counts([([pv[i] for i in a], [pv[i] for i in s]) for a, s in groups])]
+    def pipeline():
+        pipe = make_pipe([([0, 1], [4])]); pipe.complete()
+        return int(agg.combine_and_sub(pipe)[0]) == expect([([0, 1], [4])])[0]
+    # 40 groups: the staged many-groups tables (pipeline_create uploads the plane masks)
+    many = [([g % 2, 2 + g % 4], [2 + (g + 1) % 4]) for g in range(40)]
+    exp_many = expect(many)
+    def pipeline_staged():
+        pipe = make_pipe(many); pipe.complete()
+        return [int(x) for x in agg.combine_and_sub(pipe)] == exp_many
+    # GAP-only groups under a search limit, through the asynchronous entry (limit_counts_run_dev)
+    gap_groups = [([2, 3], []), ([2, 4], [5]), ([3, 4, 5], []), ([4], [2]), ([2, 5], [3]), ([5], [])]
+    exp_gap, lim = expect(gap_groups), 5
+    def pipeline_limit_dev():
+        pipe = make_pipe(gap_groups); pipe.set_search_count_limit(lim); pipe.complete()
+        d = torch.full((len(gap_groups),), -1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        agg.run_counts_dev(pipe, d.data_ptr())
+        c.synchronize()
+        got = [int(x) for x in d.cpu().tolist()]
+        return all(min(lim, t) <= g <= t for g, t in zip(got, exp_gap))
+    # asynchronous results over GAP operands: a pending operand, the pending scratch and the wait's slab trim
+    exp_async = port.count_op2(0, port.agg_or([pv[2], pv[3]]), pv[4])
+    def op2_async():
+        p1 = bm.bvector.op2_async(bm.OR, vs[2], vs[3])
+        p2 = bm.bvector.op2_async(bm.AND, p1, vs[4])
+        return p2.wait().count() == exp_async
+    exp_and_sub = port.agg_and_sub([pv[0], pv[1]], [pv[4]]).count()
+    def and_sub_materialised():
+        t, _ = agg.combine_and_sub([vs[0], vs[1]], [vs[4]])
+        return t.count() == exp_and_sub
+    bt = vs[4].block_table()
+    def upload_gap():
+        u = bm.bvector.from_block_table(c, nbits, *bt)
+        return u.count() == pv[4].count()
+    exp_dist = np.array([[port.count_op2(0, pv[i], pv[j]) for j in (2, 3, 4)] for i in (2, 3, 4)], np.uint64)
+    def distance_gap(): return (bm.distance_matrix([vs[2], vs[3], vs[4]])[0] == exp_dist).all()
+    # ONE pipeline run again and again, its groups served by a prepared AND collection through the member directory: the member
+    # table is built at the first run after the collections change (set_tuning bumps that at the end of a run that succeeded),
+    # so a run whose table allocation failed is followed by a run of the same pipeline that must not use a table it does not have
+    served_groups = [([2, 3], []), ([2, 4], []), ([3, 4, 5], []), ([4, 5], [])]
+    exp_served, served = expect(served_groups), []
+    def pipeline_coll_served():
+        first = not served
+        if first:
+            c.collection_prepare([vs[i] for i in (2, 3, 4, 5)], bm.ROLE_AND)
+            c.set_tuning("coll_members", 1)
+            served.append(make_pipe(served_groups)); served[0].complete()
+        ok = [int(x) for x in agg.combine_and_sub(served[0])] == exp_served
+        if first: assert "k_coll_members" in served[0].describe()        # (the path this family is about)
+        c.set_tuning("coll_members", 1)
+        return ok
+    for name, fn in (("pairwise", pairwise), ("combine_or", combine_or), ("rs_index", rs_index), ("prepare", prepare), ("pipeline", pipeline),
+                     ("pipeline_staged", pipeline_staged), ("pipeline_limit_dev", pipeline_limit_dev), ("op2_async", op2_async),
+                     ("and_sub_materialised", and_sub_materialised), ("upload_gap", upload_gap), ("distance_gap", distance_gap),
+                     ("pipeline_coll_served", pipeline_coll_served)):
         assert fn(), name                                 # warm: pooled blocks, scratch sized
         c.synchronize(); c.trim()
         base = c.mem_used()
-        failed = 0
-        for k in range(0, 40):
-            c.inject_failure(4, k)
-            try:
-                ok = fn()
-                assert ok, (name, k)
-            except bm.BmxError as e:
-                assert e.status == 1, (name, k, str(e))
-                failed += 1
-            finally:
-                c.inject_failure(0, 0)
+        for kind in (4, 6):
+            failed = 0
+            for k in range(0, 40):
+                c.inject_failure(kind, k)
+                try:
+                    ok = fn()
+                    assert ok, (name, kind, k)
+                except bm.BmxError as e:
+                    assert e.status == 1, (name, kind, k, str(e))
+                    failed += 1
+                finally:
+                    c.inject_failure(0, 0)
+                c.synchronize()
+            assert fn(), (name, kind)
             c.synchronize()
-        assert fn(), name
-        c.synchronize()
-        assert failed >= 1, name                          # (every one of these calls allocates at least once)
+            assert failed >= 1, (name, kind)              # (every one of these calls allocates at least once)
         leaked = c.mem_used() - base
         assert leaked <= (2 << 20), (name, leaked)        # (pool rounding of a fresh result may differ; a lost slab would be MBs per failure)
     c.close()
