@@ -42,11 +42,14 @@ BLOCK_WORDS, BLOCK_BITS = 2048, 65536
 opt_none, opt_compress = 0, 3        # bvector::optmode (src/bm.h:129-135)
 ID_MAX = 0xFFFFFFFF                  # bm::id_max (src/bmconst.h:109)
 ID_MAX64 = 0xFFFFFFFFFFFFFFFF
+# bm::sort_order (src/bmconst.h:204-210): what the caller knows about the order of an id list
+BM_UNSORTED, BM_SORTED, BM_SORTED_UNIFORM, BM_UNKNOWN = 0, 1, 2, 3
 
 __all__ = ["context", "bvector", "aggregator", "slice_scanner", "rs_index", "group", "gbvector", "gaggregator", "gpipeline", "bit_import_u32", "count_and", "count_or",
            "count_xor", "count_sub", "distance_operation", "distance_matrix", "distance_matrix_dev",
            "COUNT_AND", "COUNT_XOR", "COUNT_OR", "COUNT_SUB_AB", "COUNT_SUB_BA", "COUNT_A", "COUNT_B", "BmxError", "simd_version", "device_count", "agg_run_options",
-           "agg_opt_only_counts", "agg_opt_bvect_and_counts", "agg_opt_disable_bvects_and_counts"]
+           "agg_opt_only_counts", "agg_opt_bvect_and_counts", "agg_opt_disable_bvects_and_counts",
+           "BM_UNSORTED", "BM_SORTED", "BM_SORTED_UNIFORM", "BM_UNKNOWN"]
 
 
 def simd_version() -> int:
@@ -169,6 +172,45 @@ class bvector:
         check(lib().bmx_vec_generate_shard(ctx._h, seed, vec_id, int(with_common), density_q16, nbits,
                                            nb_from, nb_to, int(optimize), C.byref(h)))
         return bvector(ctx, h)
+
+    @staticmethod
+    def from_indices(ctx: context, ids, nbits: int = 0, sort_order: int = BM_UNKNOWN, optimize: bool = False) -> "bvector":
+        """bvector::set(ids, n, sort_order) on an empty vector of nbits bits (src/bm.h:4153; bmx_vec_from_indices): a vector of
+        max(nbits, max(ids) + 1) bits.  ids: a NumPy array (or anything np.asarray takes), or a contiguous torch tensor on the GPU,
+        read in place (bmx_vec_from_indices_dev: the tensor must be ready for the context's stream, e.g. after
+        torch.cuda.synchronize()); 32-bit integers -> width 4, 64-bit -> width 8"""
+        h = C.c_void_p()
+        hold, arg, width, n, dev = _ids_arg(ids)
+        fn = lib().bmx_vec_from_indices_dev if dev else lib().bmx_vec_from_indices
+        check(fn(ctx._h, arg, width, n, int(sort_order), int(nbits), int(bool(optimize)), C.byref(h)))
+        return bvector(ctx, h)
+
+    def _adopt(self, other: "bvector") -> "bvector":
+        if self._h and self.ctx._h:
+            lib().bmx_vec_free(self.ctx._h, self._h)
+        self._h, other._h = other._h, None
+        return self
+
+    def _combine_ids(self, op: int, ids, sort_order: int) -> "bvector":
+        """this = this OP (the vector of ids, as long as this one): bmx_op2 keeps the longer size (src/bm.h:6683)"""
+        if _ids_arg(ids)[3] == 0:
+            if op == AND:                                   # keep(): no ids clears the vector (src/bm.h:4179)
+                return self._adopt(bvector.from_indices(self.ctx, np.zeros(0, np.uint32), self.size()))
+            return self                                     # set() / clear(): nothing to do
+        imp = bvector.from_indices(self.ctx, ids, self.size(), sort_order, False)
+        return self._adopt(bvector._op2(op, self, imp, opt_none))
+
+    def set(self, ids, sort_order: int = BM_UNKNOWN) -> "bvector":
+        """bvector::set(ids, n, so)  src/bm.h:4153: OR with the id set"""
+        return self._combine_ids(OR, ids, sort_order)
+
+    def keep(self, ids, sort_order: int = BM_UNKNOWN) -> "bvector":
+        """bvector::keep(ids, n, so)  src/bm.h:4172: AND with the id set"""
+        return self._combine_ids(AND, ids, sort_order)
+
+    def clear(self, ids, sort_order: int = BM_UNKNOWN) -> "bvector":
+        """bvector::clear(ids, n, so)  src/bm.h:4216: SUB of the id set"""
+        return self._combine_ids(SUB, ids, sort_order)
 
     # ---- inspection -------------------------------------------------------
     def info(self):
@@ -340,6 +382,29 @@ class bvector:
         if np.isscalar(rank):
             return bool(found[0]), int(pos[0])
         return found.astype(bool), pos
+
+
+_ID_DTYPES = ("torch.int32", "torch.uint32", "torch.int64", "torch.uint64")
+
+
+def _ids_arg(ids):
+    """-> (array, pointer, width, n, on_device) of an id list (the array keeps the memory alive): a contiguous torch tensor on
+    the GPU is read in place; anything else goes through a contiguous NumPy array of 32- or 64-bit integers"""
+    if type(ids).__module__.startswith("torch"):
+        if ids.is_cuda:
+            if str(ids.dtype) not in _ID_DTYPES:
+                raise TypeError(f"ids must be 32- or 64-bit integers, not {ids.dtype}")
+            if not ids.is_contiguous():
+                raise ValueError("a device id tensor must be contiguous")
+            return ids, (C.c_void_p(ids.data_ptr()) if ids.numel() else None), ids.element_size(), ids.numel(), True
+        ids = ids.numpy()
+    a = np.asarray(ids).reshape(-1)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError(f"ids must be integers, not {a.dtype}")
+    if a.dtype.kind not in "iu" or a.dtype.itemsize not in (4, 8):
+        a = a.astype(np.uint64 if a.dtype.itemsize > 4 else np.uint32)
+    a = np.ascontiguousarray(a)
+    return a, (_ptr(a) if a.size else None), a.dtype.itemsize, a.size, False
 
 
 class rs_index:
@@ -1106,6 +1171,14 @@ class gbvector:
                  with_common: bool = False, optimize: bool = True) -> "gbvector":
         h = C.c_void_p()
         check(lib().bmx_gvec_generate(grp._h, seed, vec_id, int(with_common), density_q16, nbits, int(optimize), C.byref(h)))
+        return gbvector(grp, h)
+
+    @staticmethod
+    def from_indices(grp: group, ids, nbits: int = 0, sort_order: int = BM_UNKNOWN, optimize: bool = False) -> "gbvector":
+        """bvector.from_indices for a group (bmx_gvec_from_indices): every member imports the ids of its block range"""
+        hold, arg, width, n, _ = _ids_arg(ids.cpu() if type(ids).__module__.startswith("torch") else ids)
+        h = C.c_void_p()
+        check(lib().bmx_gvec_from_indices(grp._h, arg, width, n, int(sort_order), int(nbits), int(bool(optimize)), C.byref(h)))
         return gbvector(grp, h)
 
     def info(self):

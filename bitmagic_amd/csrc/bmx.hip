@@ -15,6 +15,7 @@
 #include "bmx_kernels10.h"
 #include "bmx_kernels11.h"
 #include "bmx_kernels12.h"
+#include "bmx_kernels13.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1436,6 +1437,189 @@ int bmx_vec_generate(bmx_ctx* ctx, uint64_t seed, uint32_t vec_id, int with_comm
                      uint32_t density_q16, uint64_t nbits, int optimize, bmx_vec** out)
 { ABI_TRY
     return bmx_vec_generate_shard(ctx, seed, vec_id, with_common, density_q16, nbits, 0u, 0xFFFFFFFFu, optimize, out);
+ABI_END }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------
+// vectors from lists of bit positions (bmx_kernels13.h): bvector::set(ids, n, sort_order) on an empty vector of nbits bits
+// ---------------------------------------------------------------------------
+#define IDS_MAX_BLOCKS (65536u * 16u)          // the limit of bmx_vec_import_bits / bmx_vec_generate: 2^20 blocks
+
+// the checks every entry makes before it touches a device (ctx and out are the caller's)
+static int ids_args(const void* ids, int width, uint64_t n, int sort_order, uint64_t nbits, const void* out)
+{
+    ARGCHK(width == 4 || width == 8);
+    ARGCHK(n == 0 || ids);
+    ARGCHK(sort_order >= BMX_UNSORTED && sort_order <= BMX_UNKNOWN);
+    ARGCHK(out);
+    if (n > 0xFFFFFFFFull) { g_last_error = "more than 2^32 - 1 ids in one call"; return BMX_ERR_RANGE; }
+    if (nbits > (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    return BMX_OK;
+}
+
+template <class T>
+static int ids_import_t(bmx_ctx* ctx, const T* d_ids, uint64_t n, uint64_t nbits, uint32_t nb_from, uint32_t nb_to,
+                        int optimize, bmx_vec** out)
+{
+    int rc;
+    // 1. largest id and order: the size of the vector, the path
+    uint64_t max_id = 0; bool sorted = true;
+    const uint32_t nchunks = (uint32_t)((n + IDS_CHUNK - 1) / IDS_CHUNK);
+    DevBuf d_chunks(ctx);
+    if (n) {
+        DevBuf d_cmax(ctx);
+        if ((rc = dmalloc(ctx, &d_chunks.p, (size_t)nchunks * 4)) || (rc = dmalloc(ctx, &d_cmax.p, (size_t)nchunks * 8))) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_scan<T>), dim3(nchunks), dim3(256), 0, ctx->stream, d_ids, (u64)n, (u32*)d_chunks, (u64*)d_cmax);
+        hipLaunchKernelGGL(k_ids_reduce, dim3(1), dim3(1024), 0, ctx->stream, (u32*)d_chunks, (const u64*)d_cmax, nchunks, ctx->d_small);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        max_id = ctx->h_small[0]; sorted = ctx->h_small[1] == 0;
+        if (max_id >= (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "id beyond the 2^20-block limit"; return BMX_ERR_RANGE; }
+        nbits = std::max<uint64_t>(nbits, max_id + 1);                              // sync_size (src/bm.h:2516)
+    }
+    const uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nb_to > nblocks64) nb_to = (uint32_t)nblocks64;
+    if (nb_from > nb_to) { g_last_error = "nb_from > nb_to"; return BMX_ERR_RANGE; }
+    const uint32_t nbl = nb_to - nb_from;
+    const uint64_t lo = (uint64_t)nb_from * BMX_BLOCK_BITS, hi = std::min<uint64_t>(nbits, (uint64_t)nb_to * BMX_BLOCK_BITS);
+    Owned<bmx_vec> v = vec_alloc_host(ctx, hi > lo ? hi - lo : 0, nbl);
+    if (!n || !nbl) {
+        if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
+        if (nbl) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nbl * 8, ctx->stream));
+        v->counts[BMX_NULL] = nbl;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *out = v.release();
+        return BMX_OK;
+    }
+    // 2. the touched blocks in block order: tblk[t] = block, ids of entry t = src[tbeg[t] .. tbeg[t + 1])
+    u32* d_tot = (u32*)(ctx->d_small + 8);                                          // {sum, touched blocks}
+    const uint32_t cap = sorted ? (uint32_t)std::min<uint64_t>(n, (max_id >> 16) + 1) : (uint32_t)std::min<uint64_t>(n, nbl);
+    DevBuf d_part(ctx), d_tblk(ctx), d_tbeg(ctx), d_cnt(ctx), d_bstart(ctx), d_bucket(ctx), d_st(ctx), d_offs(ctx);
+    if ((rc = dmalloc(ctx, &d_part.p, 256 * sizeof(uint2))) || (rc = dmalloc(ctx, &d_tblk.p, (size_t)cap * 4)) ||
+        (rc = dmalloc(ctx, &d_tbeg.p, ((size_t)cap + 1) * 4))) return rc;
+    const void* src = d_ids;
+    if (sorted) {
+        const uint32_t nparts = (nchunks + TBL_PER - 1) / TBL_PER;
+        hipLaunchKernelGGL(k_tbl_part, dim3(nparts), dim3(256), 0, ctx->stream, (const u32*)d_chunks, nchunks, (uint2*)d_part);
+        hipLaunchKernelGGL(k_tbl_top, dim3(1), dim3(256), 0, ctx->stream, (uint2*)d_part, nparts, d_tot, (u32*)nullptr);
+        hipLaunchKernelGGL(k_tbl_apply, dim3(nparts), dim3(256), 0, ctx->stream, (const u32*)d_chunks, nchunks, (const uint2*)d_part,
+                           (u32*)d_chunks, 0u, (u32*)nullptr, (u32*)nullptr);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_starts<T>), dim3(nchunks), dim3(256), 0, ctx->stream, d_ids, (u64)n,
+                           (const u32*)d_chunks, (const u32*)d_tot, (u32*)d_tblk, (u32*)d_tbeg);
+        KCHK();
+        // (the runs of a sorted list are at most its distinct blocks: what d_tot[1] counts is d_tot[0] here)
+        HIPCHK(hipMemcpyAsync(d_tot + 1, d_tot, 4, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+        d_chunks.reset();
+        const uint32_t nparts = (nbl + TBL_PER - 1) / TBL_PER;
+        const u32 grid = (u32)std::min<uint64_t>((n + 255) / 256, 256u * 32u);
+        if ((rc = dmalloc(ctx, &d_cnt.p, (size_t)nbl * 4)) || (rc = dmalloc(ctx, &d_bstart.p, (size_t)nbl * 4)) ||
+            (rc = dmalloc(ctx, &d_bucket.p, (size_t)n * 2))) return rc;
+        // shards of <= IDS_LDS_BLOCKS blocks: histogram and scatter through LDS, <= 512 workgroups of >= 4,096 ids each
+        const bool lds = nbl <= IDS_LDS_BLOCKS;
+        const u32 lgrid = (u32)std::min<uint64_t>((n + 4095) / 4096, 512u);
+        const u64 per = (n + lgrid - 1) / lgrid;
+        const size_t lds_b = (size_t)nbl * 4;
+        HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nbl * 4, ctx->stream));
+        if (lds) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_hist_lds<T>), dim3(lgrid), dim3(256), lds_b, ctx->stream, d_ids, (u64)n, per, nb_from, nbl,
+                                    (u32*)d_cnt);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_hist<T>), dim3(grid), dim3(256), 0, ctx->stream, d_ids, (u64)n, nb_from, nbl, (u32*)d_cnt);
+        hipLaunchKernelGGL(k_tbl_part, dim3(nparts), dim3(256), 0, ctx->stream, (const u32*)d_cnt, nbl, (uint2*)d_part);
+        hipLaunchKernelGGL(k_tbl_top, dim3(1), dim3(256), 0, ctx->stream, (uint2*)d_part, nparts, d_tot, (u32*)d_tbeg);
+        hipLaunchKernelGGL(k_tbl_apply, dim3(nparts), dim3(256), 0, ctx->stream, (const u32*)d_cnt, nbl, (const uint2*)d_part,
+                           (u32*)d_bstart, nb_from, (u32*)d_tblk, (u32*)d_tbeg);
+        if (lds) {
+            HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nbl * 4, ctx->stream));          // (the cursors of the buckets)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_scatter_lds<T>), dim3(lgrid), dim3(256), lds_b, ctx->stream, d_ids, (u64)n, per, nb_from,
+                               nbl, (const u32*)d_bstart, (u32*)d_cnt, (u16*)d_bucket);
+        } else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_scatter<T>), dim3(grid), dim3(256), 0, ctx->stream, d_ids, (u64)n, nb_from, nbl,
+                                  (const u32*)d_bstart, (u32*)d_cnt, (u16*)d_bucket);
+        KCHK();
+        d_cnt.reset(); d_bstart.reset();                          // (pooled: the next user is enqueued behind the scatter)
+        src = d_bucket.p;
+    }
+    // 3. stats and layout of the touched blocks
+    if ((rc = dmalloc(ctx, &d_st.p, (size_t)cap * sizeof(BlockStat))) || (rc = dmalloc(ctx, &d_offs.p, (size_t)cap * 4))) return rc;
+    const dim3 wgrid((cap + 3) / 4);
+    if (sorted) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_stats<T>), wgrid, dim3(256), 0, ctx->stream, (const T*)src, (const u32*)d_tblk,
+                                   (const u32*)d_tbeg, (const u32*)d_tot, cap, nb_from, nbl, optimize, (BlockStat*)d_st);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_stats<u16>), wgrid, dim3(256), 0, ctx->stream, (const u16*)src, (const u32*)d_tblk,
+                            (const u32*)d_tbeg, (const u32*)d_tot, cap, nb_from, nbl, optimize, (BlockStat*)d_st);
+    KCHK();
+    hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, (const BlockStat*)d_st, cap, (u32*)d_offs, ctx->d_small);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint32_t n_bit = (uint32_t)ctx->h_small[0]; const uint64_t gap_words = ctx->h_small[1];
+    v->counts[BMX_BIT] = (uint32_t)ctx->h_small[2 + K_BIT]; v->counts[BMX_GAP] = (uint32_t)ctx->h_small[2 + K_GAP];
+    v->counts[BMX_FULL] = (uint32_t)ctx->h_small[2 + K_FULL];
+    v->counts[BMX_NULL] = nbl - v->counts[BMX_BIT] - v->counts[BMX_GAP] - v->counts[BMX_FULL];   // (untouched blocks too)
+    // 4. the vector: NULL descriptors, then the touched blocks
+    if ((rc = vec_alloc_device(v.get(), n_bit, gap_words))) return rc;
+    HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nbl * 8, ctx->stream));
+    if (sorted) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_emit<T>), wgrid, dim3(256), 0, ctx->stream, (const T*)src, (const u32*)d_tblk,
+                                   (const u32*)d_tbeg, (const u32*)d_tot, cap, nb_from, nbl, (const BlockStat*)d_st, (const u32*)d_offs,
+                                   v->d_bits, v->d_gaps, v->d_desc);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_emit<u16>), wgrid, dim3(256), 0, ctx->stream, (const u16*)src, (const u32*)d_tblk,
+                            (const u32*)d_tbeg, (const u32*)d_tot, cap, nb_from, nbl, (const BlockStat*)d_st, (const u32*)d_offs,
+                            v->d_bits, v->d_gaps, v->d_desc);
+    KCHK();
+    if ((rc = vec_build_tdir(ctx, v.get()))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *out = v.release();
+    return BMX_OK;
+}
+
+// d_ids: device memory, ready on the context's stream
+static int ids_import(bmx_ctx* ctx, const void* d_ids, int width, uint64_t n, uint64_t nbits, uint32_t nb_from, uint32_t nb_to,
+                      int optimize, bmx_vec** out)
+{
+    return width == 8 ? ids_import_t(ctx, (const u64*)d_ids, n, nbits, nb_from, nb_to, optimize, out)
+                      : ids_import_t(ctx, (const u32*)d_ids, n, nbits, nb_from, nb_to, optimize, out);
+}
+
+static int ids_import_host(bmx_ctx* ctx, const void* ids, int width, uint64_t n, uint64_t nbits, uint32_t nb_from, uint32_t nb_to,
+                           int optimize, bmx_vec** out)
+{
+    int rc = set_dev(ctx); if (rc) return rc;
+    DevBuf d_ids(ctx);
+    if (n) {
+        if ((rc = dmalloc(ctx, &d_ids.p, (size_t)n * (size_t)width))) return rc;
+        HIPCHK(hipMemcpyAsync(d_ids.p, ids, (size_t)n * (size_t)width, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return ids_import(ctx, d_ids.p, width, n, nbits, nb_from, nb_to, optimize, out);
+}
+
+extern "C" {
+
+int bmx_vec_from_indices(bmx_ctx* ctx, const void* ids, int width, uint64_t n, int sort_order,
+                         uint64_t nbits, int optimize, bmx_vec** out)
+{ ABI_TRY
+    int rc = ids_args(ids, width, n, sort_order, nbits, out); if (rc) return rc;
+    *out = nullptr;
+    ARGCHK(ctx);
+    return ids_import_host(ctx, ids, width, n, nbits, 0u, 0xFFFFFFFFu, optimize, out);
+ABI_END }
+
+int bmx_vec_from_indices_dev(bmx_ctx* ctx, const void* d_ids, int width, uint64_t n, int sort_order,
+                             uint64_t nbits, int optimize, bmx_vec** out)
+{ ABI_TRY
+    int rc = ids_args(d_ids, width, n, sort_order, nbits, out); if (rc) return rc;
+    *out = nullptr;
+    ARGCHK(ctx);
+    if ((rc = set_dev(ctx))) return rc;
+    return ids_import(ctx, d_ids, width, n, nbits, 0u, 0xFFFFFFFFu, optimize, out);
+ABI_END }
+
+int bmx_vec_from_indices_shard(bmx_ctx* ctx, const void* ids, int width, uint64_t n, int sort_order, uint64_t nbits,
+                               uint32_t nb_from, uint32_t nb_to, int optimize, bmx_vec** out)
+{ ABI_TRY
+    int rc = ids_args(ids, width, n, sort_order, nbits, out); if (rc) return rc;
+    *out = nullptr;
+    ARGCHK(ctx);
+    return ids_import_host(ctx, ids, width, n, nbits, nb_from, nb_to, optimize, out);
 ABI_END }
 
 } // extern "C"

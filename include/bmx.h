@@ -124,6 +124,28 @@ int bmx_vec_generate_shard(bmx_ctx* ctx, uint64_t seed, uint32_t vec_id, int wit
                            uint32_t density_q16, uint64_t nbits, uint32_t nb_from, uint32_t nb_to,
                            int optimize, bmx_vec** out);
 int bmx_vec_free(bmx_ctx* ctx, bmx_vec* v);
+/* ---- vectors from lists of bit positions ---- */
+/* bm::sort_order (src/bmconst.h:204-210): what the caller knows about the order of an id list */
+#define BMX_UNSORTED       0
+#define BMX_SORTED         1   /* ids do not decrease: checked on the device; a list that does not keep it takes the unsorted path */
+#define BMX_SORTED_UNIFORM 2
+#define BMX_UNKNOWN        3
+/* bvector::set(ids, n, sort_order) on an empty vector of nbits bits: import / import_sorted / import_block
+ * src/bm.h:4153,4312,4364,4430.  ids: n positions of width 4 (uint32_t) or 8 (uint64_t) bytes, any order, duplicates
+ * allowed.  The vector has max(nbits, largest id + 1) bits (sync_size, src/bm.h:2516; nbits = 0: sized by the ids), at most
+ * 2^20 blocks and n < 2^32 (else BMX_ERR_RANGE).  Blocks no id touches are NULL.  optimize = 0: every touched block is a
+ * bit-block (import_block); optimize != 0: FULL, GAP (< 1,276 runs) or bit-block by the rule of bmx_vec_import_bits
+ * (optimize_bit_block, src/bmblocks.h:1414-1436).  The reference's import_sorted(.., true) leaves the last block of the list
+ * unoptimised unless its bit 65,535 is set; here every touched block is: the content is the same.  The block table does not
+ * depend on sort_order or on the order of the ids.  Device memory and time follow n and the touched blocks, not nbits.
+ * _dev: the ids are device memory, ready on the context's stream (bmx_vec_to_indices_dev's output, a framework's tensor). */
+int bmx_vec_from_indices(bmx_ctx* ctx, const void* ids, int width, uint64_t n, int sort_order,
+                         uint64_t nbits, int optimize, bmx_vec** out);
+int bmx_vec_from_indices_dev(bmx_ctx* ctx, const void* d_ids, int width, uint64_t n, int sort_order,
+                             uint64_t nbits, int optimize, bmx_vec** out);
+/* blocks [nb_from, nb_to) of the vector above, rebased like bmx_vec_generate_shard; ids outside the range are dropped */
+int bmx_vec_from_indices_shard(bmx_ctx* ctx, const void* ids, int width, uint64_t n, int sort_order, uint64_t nbits,
+                               uint32_t nb_from, uint32_t nb_to, int optimize, bmx_vec** out);
 /* bvector::calc_stat (src/bm.h:4010): counts[kind]; bit_slab_blocks / gap_words =
  * sizes (8 KiB blocks / uint16 words) of the two slabs bmx_vec_download fills.
  * Result vectors keep one slab slot per block column, so bit_slab_blocks may
@@ -449,6 +471,10 @@ int bmx_gvec_upload(bmx_group* g, uint64_t nbits, uint32_t nblocks,
 /* bmx_vec_generate for a group: every member generates its own block range (bmx_vec_generate_shard) */
 int bmx_gvec_generate(bmx_group* g, uint64_t seed, uint32_t vec_id, int with_common,
                       uint32_t density_q16, uint64_t nbits, int optimize, bmx_gvec** out);
+/* bmx_vec_from_indices for a group: sized as the single form, cut at the group's partition; every member imports the ids of
+ * its block range (bmx_vec_from_indices_shard) */
+int bmx_gvec_from_indices(bmx_group* g, const void* ids, int width, uint64_t n, int sort_order,
+                          uint64_t nbits, int optimize, bmx_gvec** out);
 int bmx_gvec_free(bmx_group* g, bmx_gvec* v);
 /* totals over the shards; bit_slab_blocks / gap_words size the buffers of bmx_gvec_download */
 int bmx_gvec_info(const bmx_gvec* v, uint64_t* nbits, uint32_t* nblocks, uint32_t counts[4],

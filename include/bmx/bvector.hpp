@@ -53,6 +53,9 @@ inline void check(int rc)
 
 typedef uint64_t size_type;
 
+/// bm::sort_order (src/bmconst.h:204-210)
+enum sort_order { BM_UNSORTED = BMX_UNSORTED, BM_SORTED = BMX_SORTED, BM_SORTED_UNIFORM = BMX_SORTED_UNIFORM, BM_UNKNOWN = BMX_UNKNOWN };
+
 /// one device + one HIP stream
 class context {
 public:
@@ -144,6 +147,27 @@ public:
 
     /// bvector<>::count()  src/bm.h:2431
     size_type count() const { uint64_t c = 0; if (h_) check(bmx_count(ctx_->handle(), h_, &c)); return c; }
+
+    /// bvector<>::set(ids, n, so)  src/bm.h:4153: OR with the set of ids (bmx_vec_from_indices, then bmx_op2)
+    void set(const size_type* ids, size_type n, sort_order so = BM_UNKNOWN) { combine_ids(BMX_OR, ids, 8, n, so); }
+    void set(const uint32_t* ids, size_type n, sort_order so = BM_UNKNOWN) { combine_ids(BMX_OR, ids, 4, n, so); }
+    /// bvector<>::keep(ids, n, so)  src/bm.h:4172: AND with the set of ids; no ids clears the vector
+    void keep(const size_type* ids, size_type n, sort_order so = BM_UNKNOWN) { combine_ids(BMX_AND, ids, 8, n, so); }
+    void keep(const uint32_t* ids, size_type n, sort_order so = BM_UNKNOWN) { combine_ids(BMX_AND, ids, 4, n, so); }
+    /// bvector<>::clear(ids, n, so)  src/bm.h:4216: SUB of the set of ids
+    void clear(const size_type* ids, size_type n, sort_order so = BM_UNKNOWN) { combine_ids(BMX_SUB, ids, 8, n, so); }
+    void clear(const uint32_t* ids, size_type n, sort_order so = BM_UNKNOWN) { combine_ids(BMX_SUB, ids, 4, n, so); }
+    /// bvector<>::import_sorted(ids, n, opt_flag)  src/bm.h:4364: ids that do not decrease, ORed in; opt_flag compresses the
+    /// touched blocks (every one of them here, the last one of the list too: the same content, src/bm.h:4364-4425)
+    void import_sorted(const size_type* ids, size_type n, bool opt_flag)
+    {
+        if (!ids || !n) return;
+        bmx_vec* r = nullptr;
+        check(bmx_vec_from_indices(ctx_->handle(), ids, 8, n, BMX_SORTED, size(), opt_flag, &r));
+        if (!h_) { adopt(r); return; }
+        bvector imp(*ctx_); imp.adopt(r);
+        op2(BMX_OR, imp, opt_flag ? opt_compress : opt_none);
+    }
     /// the sorted positions of the set bits (device compaction, bmx_vec_to_indices): what bm::bvector<>::enumerator or
     /// bm::for_each_bit would feed into a container, in one call
     void to_indices(std::vector<size_type>& out) const
@@ -272,6 +296,23 @@ private:
         check(bmx_op2(ctx_->handle(), op, h_, b.h_, opt == opt_compress, &r));
         adopt(r);
         return *this;
+    }
+    // this = this OP (the vector of the ids, as long as this one); bmx_op2 keeps the longer size (src/bm.h:6683)
+    void combine_ids(int op, const void* ids, int width, size_type n, sort_order so)
+    {
+        if (!ids || !n) {                                  // set / clear: nothing to do; keep: the vector is cleared
+            if (op != BMX_AND || !h_) return;
+            bmx_vec* r = nullptr;
+            check(bmx_vec_from_indices(ctx_->handle(), nullptr, 4, 0, so, size(), 0, &r));
+            adopt(r);
+            return;
+        }
+        if (!h_ && op != BMX_OR) return;                   // (src/bm.h:4176, 4220: nothing to keep or clear)
+        bmx_vec* r = nullptr;
+        check(bmx_vec_from_indices(ctx_->handle(), ids, width, n, so, size(), 0, &r));
+        if (!h_) { adopt(r); return; }
+        bvector imp(*ctx_); imp.adopt(r);
+        op2(op, imp, opt_none);
     }
     context* ctx_;
     bmx_vec* h_ = nullptr;

@@ -97,6 +97,19 @@ public:
         check(bmx_gvec_upload(grp_->handle(), nbits, nblocks, kinds, offs, bit_slab, n_bit_blocks, gap_slab, gap_words, &h));
         adopt(h);
     }
+    /// bvector<>::set(ids, n, so) on an empty vector of nbits bits, for the group (bmx_gvec_from_indices)
+    void assign_indices(const size_type* ids, size_type n, sort_order so = BM_UNKNOWN, size_type nbits = 0, bool optimize = false)
+    {
+        bmx_gvec* h = nullptr;
+        check(bmx_gvec_from_indices(grp_->handle(), ids, 8, n, so, nbits, optimize, &h));
+        adopt(h);
+    }
+    void assign_indices(const uint32_t* ids, size_type n, sort_order so = BM_UNKNOWN, size_type nbits = 0, bool optimize = false)
+    {
+        bmx_gvec* h = nullptr;
+        check(bmx_gvec_from_indices(grp_->handle(), ids, 4, n, so, nbits, optimize, &h));
+        adopt(h);
+    }
     size_type size() const { uint64_t n = 0; if (h_) check(bmx_gvec_info(h_, &n, nullptr, nullptr, nullptr, nullptr)); return n; }
     uint32_t block_count() const { uint32_t n = 0; if (h_) check(bmx_gvec_info(h_, nullptr, &n, nullptr, nullptr, nullptr)); return n; }
     void calc_stat(bvector::statistics* st) const
