@@ -185,6 +185,34 @@ class bvector:
         check(fn(ctx._h, arg, width, n, int(sort_order), int(nbits), int(bool(optimize)), C.byref(h)))
         return bvector(ctx, h)
 
+    @staticmethod
+    def from_ranges(ctx: context, ranges, nbits: int = 0) -> "bvector":
+        """bvector::set_range(l, r) (src/bm.h:2398) for every pair on an empty vector of nbits bits, then optimize()
+        (bmx_vec_from_ranges): a vector of max(nbits, largest end + 1) bits.  ranges: an (n, 2) NumPy array (or anything
+        np.asarray takes) of inclusive [left, right] pairs in any order, or a contiguous (n, 2) torch tensor on the GPU, read
+        in place (bmx_vec_from_ranges_dev); 32-bit integers -> width 4, 64-bit -> width 8"""
+        h = C.c_void_p()
+        hold, arg, width, n, dev = _ranges_arg(ranges)
+        fn = lib().bmx_vec_from_ranges_dev if dev else lib().bmx_vec_from_ranges
+        check(fn(ctx._h, arg, width, n, int(nbits), C.byref(h)))
+        return bvector(ctx, h)
+
+    def _combine_range(self, op: int, left: int, right: int) -> "bvector":
+        imp = bvector.from_ranges(self.ctx, np.array([[left, right]], np.uint64), self.size())
+        return self._adopt(bvector._op2(op, self, imp, opt_none))
+
+    def set_range(self, left: int, right: int, value: bool = True) -> "bvector":
+        """bvector::set_range(left, right, value)  src/bm.h:2398: both ends inclusive, swapped when right < left"""
+        return self._combine_range(OR if value else SUB, left, right)
+
+    def clear_range(self, left: int, right: int) -> "bvector":
+        """bvector::clear_range(left, right)  src/bm.h:2383"""
+        return self._combine_range(SUB, left, right)
+
+    def keep_range(self, left: int, right: int) -> "bvector":
+        """bvector::keep_range(left, right)  src/bm.h:7908: everything outside the range is cleared"""
+        return self._combine_range(AND, left, right)
+
     def _adopt(self, other: "bvector") -> "bvector":
         if self._h and self.ctx._h:
             lib().bmx_vec_free(self.ctx._h, self._h)
@@ -227,6 +255,29 @@ class bvector:
         out = np.zeros(cnt, np.uint64 if width == 8 else np.uint32)
         check(lib().bmx_vec_to_indices(self.ctx._h, self._h, width, _ptr(out) if cnt else None, cnt, C.byref(n)))
         return out[:n.value]
+
+    def to_ranges(self, width: int = 8) -> np.ndarray:
+        """the maximal runs of ones as an (n, 2) array of inclusive [left, right] pairs, ascending: what a
+        bm::interval_enumerator loop yields (src/bmintervals.h:52-226; bmx_vec_to_ranges)"""
+        dt = np.uint64 if width == 8 else np.uint32
+        n = C.c_uint64()
+        rc = lib().bmx_vec_to_ranges(self.ctx._h, self._h, width, None, 0, C.byref(n))     # (the number of intervals first)
+        if rc != 0 and not (rc == _ffi.ERR_RANGE and n.value):
+            check(rc)
+        out = np.zeros((n.value, 2), dt)
+        if n.value:
+            check(lib().bmx_vec_to_ranges(self.ctx._h, self._h, width, _ptr(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def to_ranges_dev(self, out, width: int = 8) -> int:
+        """bmx_vec_to_ranges_dev: the intervals into `out`, a contiguous torch tensor on the GPU of 32- or 64-bit integers
+        (width from its dtype) with room for out.numel() // 2 pairs; -> the number of intervals"""
+        hold, arg, w, cnt, dev = _ids_arg(out)
+        if not dev:
+            raise TypeError("to_ranges_dev writes into a tensor on the GPU")
+        n = C.c_uint64()
+        check(lib().bmx_vec_to_ranges_dev(self.ctx._h, self._h, w, arg, cnt // 2, C.byref(n)))
+        return n.value
 
     def operand_bytes(self) -> int:
         """algorithmic bytes of this operand: 8,192 B per bit-block, 2 x (len + 1) B per GAP block"""
@@ -405,6 +456,17 @@ def _ids_arg(ids):
         a = a.astype(np.uint64 if a.dtype.itemsize > 4 else np.uint32)
     a = np.ascontiguousarray(a)
     return a, (_ptr(a) if a.size else None), a.dtype.itemsize, a.size, False
+
+
+def _ranges_arg(ranges):
+    """-> (array, pointer, width, n pairs, on_device) of an (n, 2) list of inclusive pairs, through the checks of _ids_arg"""
+    shape = tuple(ranges.shape) if hasattr(ranges, "shape") else np.asarray(ranges).shape
+    if len(shape) == 1 and shape[0] == 0:
+        shape = (0, 2)
+    if len(shape) != 2 or shape[1] != 2:
+        raise ValueError(f"ranges must have shape (n, 2), not {shape}")
+    hold, arg, width, cnt, dev = _ids_arg(ranges)
+    return hold, arg, width, cnt // 2, dev
 
 
 class rs_index:
@@ -1179,6 +1241,14 @@ class gbvector:
         hold, arg, width, n, _ = _ids_arg(ids.cpu() if type(ids).__module__.startswith("torch") else ids)
         h = C.c_void_p()
         check(lib().bmx_gvec_from_indices(grp._h, arg, width, n, int(sort_order), int(nbits), int(bool(optimize)), C.byref(h)))
+        return gbvector(grp, h)
+
+    @staticmethod
+    def from_ranges(grp: group, ranges, nbits: int = 0) -> "gbvector":
+        """bvector.from_ranges for a group (bmx_gvec_from_ranges): every member imports the pairs clipped to its block range"""
+        hold, arg, width, n, _ = _ranges_arg(ranges.cpu() if type(ranges).__module__.startswith("torch") else ranges)
+        h = C.c_void_p()
+        check(lib().bmx_gvec_from_ranges(grp._h, arg, width, n, int(nbits), C.byref(h)))
         return gbvector(grp, h)
 
     def info(self):

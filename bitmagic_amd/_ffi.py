@@ -64,6 +64,11 @@ def lib() -> C.CDLL:
         "bmx_vec_info": (i32, [vp, P(u64), P(u32), P(u32), P(u32), P(u64)]),
         "bmx_vec_operand_bytes": (i32, [vp, vp, P(u64)]),
         "bmx_vec_download": (i32, [vp, vp, vp, vp, vp, vp]),
+        "bmx_vec_from_ranges": (i32, [vp, vp, i32, u64, u64, P(vp)]),
+        "bmx_vec_from_ranges_dev": (i32, [vp, vp, i32, u64, u64, P(vp)]),
+        "bmx_vec_from_ranges_shard": (i32, [vp, vp, i32, u64, u64, u32, u32, P(vp)]),
+        "bmx_vec_to_ranges": (i32, [vp, vp, i32, vp, u64, P(u64)]),
+        "bmx_vec_to_ranges_dev": (i32, [vp, vp, i32, vp, u64, P(u64)]),
         "bmx_vec_to_indices": (i32, [vp, vp, i32, vp, u64, P(u64)]),
         "bmx_vec_to_indices_dev": (i32, [vp, vp, i32, vp, u64, P(u64)]),
         "bmx_agg_and_sub_indices": (i32, [vp, P(vp), C.c_size_t, P(vp), C.c_size_t, i32, vp, u64, P(u64)]),
@@ -126,6 +131,7 @@ def lib() -> C.CDLL:
         "bmx_group_rccl_ranks": (i32, [vp, P(i32)]),
         "bmx_gvec_upload": (i32, [vp, u64, u32, vp, vp, vp, u32, vp, u64, P(vp)]),
         "bmx_gvec_generate": (i32, [vp, u64, u32, i32, u32, u64, i32, P(vp)]),
+        "bmx_gvec_from_ranges": (i32, [vp, vp, i32, u64, u64, P(vp)]),
         "bmx_gvec_from_indices": (i32, [vp, vp, i32, u64, i32, u64, i32, P(vp)]),
         "bmx_gvec_free": (i32, [vp, vp]),
         "bmx_gvec_info": (i32, [vp, P(u64), P(u32), P(u32), P(u32), P(u64)]),

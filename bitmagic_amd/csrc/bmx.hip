@@ -16,6 +16,7 @@
 #include "bmx_kernels11.h"
 #include "bmx_kernels12.h"
 #include "bmx_kernels13.h"
+#include "bmx_kernels14.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1620,6 +1621,206 @@ int bmx_vec_from_indices_shard(bmx_ctx* ctx, const void* ids, int width, uint64_
     *out = nullptr;
     ARGCHK(ctx);
     return ids_import_host(ctx, ids, width, n, nbits, nb_from, nb_to, optimize, out);
+ABI_END }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------
+// vectors from lists of inclusive [left, right] pairs (bmx_kernels14.h): set_range(l, r) for every pair on an empty vector of
+// nbits bits, then optimize()
+// ---------------------------------------------------------------------------
+static int rng_args(const void* ranges, int width, uint64_t n, uint64_t nbits, const void* out)
+{
+    ARGCHK(width == 4 || width == 8);
+    ARGCHK(n == 0 || ranges);
+    ARGCHK(out);
+    if (n > 0xFFFFFFFFull) { g_last_error = "more than 2^32 - 1 pairs in one call"; return BMX_ERR_RANGE; }
+    if (nbits > (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    return BMX_OK;
+}
+
+template <class T>
+static int rng_import_t(bmx_ctx* ctx, const T* d_pairs, uint64_t n, uint64_t nbits, uint32_t nb_from, uint32_t nb_to, bmx_vec** out)
+{
+    int rc;
+    // 1. largest end and order: the size of the vector, the path
+    bool sorted = true;
+    if (n) {
+        const uint32_t nchunks = (uint32_t)((n + RNG_CHUNK - 1) / RNG_CHUNK);
+        DevBuf d_flags(ctx), d_cmax(ctx);
+        if ((rc = dmalloc(ctx, &d_flags.p, (size_t)nchunks * 4)) || (rc = dmalloc(ctx, &d_cmax.p, (size_t)nchunks * 8))) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_scan<T>), dim3(nchunks), dim3(256), 0, ctx->stream, d_pairs, (u64)n, (u32*)d_flags, (u64*)d_cmax);
+        hipLaunchKernelGGL(k_ids_reduce, dim3(1), dim3(1024), 0, ctx->stream, (u32*)d_flags, (const u64*)d_cmax, nchunks, ctx->d_small);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        const uint64_t max_end = ctx->h_small[0]; sorted = ctx->h_small[1] == 0;
+        if (max_end >= (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "range end beyond the 2^20-block limit"; return BMX_ERR_RANGE; }
+        nbits = std::max<uint64_t>(nbits, max_end + 1);
+    }
+    const uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nb_to > nblocks64) nb_to = (uint32_t)nblocks64;
+    if (nb_from > nb_to) { g_last_error = "nb_from > nb_to"; return BMX_ERR_RANGE; }
+    const uint32_t nbl = nb_to - nb_from;
+    const uint64_t lo = (uint64_t)nb_from * BMX_BLOCK_BITS, hi = std::min<uint64_t>(nbits, (uint64_t)nb_to * BMX_BLOCK_BITS);
+    Owned<bmx_vec> v = vec_alloc_host(ctx, hi > lo ? hi - lo : 0, nbl);
+    if (!n || !nbl) {
+        if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
+        if (nbl) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nbl * 8, ctx->stream));
+        v->counts[BMX_NULL] = nbl;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        *out = v.release();
+        return BMX_OK;
+    }
+    // 2. per block of the shard, in block order: its pairs (sorted and separated) or its bucket of pieces, and its stats
+    DevBuf d_st(ctx), d_offs(ctx), d_pfirst(ctx), d_pcnt(ctx), d_cnt(ctx), d_diff(ctx), d_pend(ctx), d_cover(ctx), d_bucket(ctx);
+    if ((rc = dmalloc(ctx, &d_st.p, (size_t)nbl * sizeof(BlockStat))) || (rc = dmalloc(ctx, &d_offs.p, (size_t)nbl * 4))) return rc;
+    const dim3 wgrid((nbl + 3) / 4);
+    if (sorted) {
+        if ((rc = dmalloc(ctx, &d_pfirst.p, (size_t)nbl * 4)) || (rc = dmalloc(ctx, &d_pcnt.p, (size_t)nbl * 4))) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_stats_sorted<T>), wgrid, dim3(256), 0, ctx->stream, d_pairs, (u64)n, nb_from, nbl,
+                           (BlockStat*)d_st, (u32*)d_pfirst, (u32*)d_pcnt);
+        KCHK();
+    } else {
+        if (n > 0x7FFFFFFFull) { g_last_error = "more than 2^31 - 1 pairs that are not sorted and separated"; return BMX_ERR_RANGE; }
+        const u32 grid = (u32)std::min<uint64_t>((n + 255) / 256, 256u * 32u);
+        if ((rc = dmalloc(ctx, &d_cnt.p, (size_t)nbl * 4)) || (rc = dmalloc(ctx, &d_diff.p, ((size_t)nbl + 1) * 4)) ||
+            (rc = dmalloc(ctx, &d_pend.p, (size_t)nbl * 8)) || (rc = dmalloc(ctx, &d_cover.p, (size_t)nbl * 8))) return rc;
+        HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nbl * 4, ctx->stream));
+        HIPCHK(hipMemsetAsync(d_diff.p, 0, ((size_t)nbl + 1) * 4, ctx->stream));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_count<T>), dim3(grid), dim3(256), 0, ctx->stream, d_pairs, (u64)n, nb_from, nbl,
+                           (u32*)d_cnt, (u32*)d_diff);
+        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_cnt, nbl, (u64*)d_pend, ctx->d_small);
+        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_diff, nbl, (u64*)d_cover, ctx->d_small + 1);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        const uint64_t npieces = ctx->h_small[0];                  // (<= 2 n < 2^32)
+        d_diff.reset();
+        if ((rc = dmalloc(ctx, &d_bucket.p, std::max<size_t>((size_t)npieces, 1) * 4))) return rc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_scatter<T>), dim3(grid), dim3(256), 0, ctx->stream, d_pairs, (u64)n, nb_from, nbl,
+                           (const u64*)d_pend, (u32*)d_cnt, (u32*)d_bucket);
+        hipLaunchKernelGGL(k_rng_stats_any, wgrid, dim3(256), 0, ctx->stream, (const u32*)d_bucket, (const u64*)d_pend,
+                           (const u64*)d_cover, nbl, (BlockStat*)d_st);
+        KCHK();
+        d_cnt.reset(); d_cover.reset();                           // (pooled: the next user is enqueued behind these kernels)
+    }
+    // 3. layout
+    hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, (const BlockStat*)d_st, nbl, (u32*)d_offs, ctx->d_small);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint32_t n_bit = (uint32_t)ctx->h_small[0]; const uint64_t gap_words = ctx->h_small[1];
+    v->counts[BMX_BIT] = (uint32_t)ctx->h_small[2 + K_BIT]; v->counts[BMX_GAP] = (uint32_t)ctx->h_small[2 + K_GAP];
+    v->counts[BMX_FULL] = (uint32_t)ctx->h_small[2 + K_FULL]; v->counts[BMX_NULL] = (uint32_t)ctx->h_small[2 + K_NULL];
+    // 4. the vector: every block's wave writes its descriptor
+    if ((rc = vec_alloc_device(v.get(), n_bit, gap_words))) return rc;
+    if (sorted) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_emit_sorted<T>), wgrid, dim3(256), 0, ctx->stream, d_pairs, nb_from, nbl,
+                                   (const BlockStat*)d_st, (const u32*)d_offs, (const u32*)d_pfirst, (const u32*)d_pcnt,
+                                   v->d_bits, v->d_gaps, v->d_desc);
+    else hipLaunchKernelGGL(k_rng_emit_any, wgrid, dim3(256), 0, ctx->stream, (const u32*)d_bucket, (const u64*)d_pend, nbl,
+                            (const BlockStat*)d_st, (const u32*)d_offs, v->d_bits, v->d_gaps, v->d_desc);
+    KCHK();
+    if ((rc = vec_build_tdir(ctx, v.get()))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *out = v.release();
+    return BMX_OK;
+}
+
+// d_pairs: device memory, ready on the context's stream
+static int rng_import(bmx_ctx* ctx, const void* d_pairs, int width, uint64_t n, uint64_t nbits, uint32_t nb_from, uint32_t nb_to,
+                      bmx_vec** out)
+{
+    return width == 8 ? rng_import_t(ctx, (const u64*)d_pairs, n, nbits, nb_from, nb_to, out)
+                      : rng_import_t(ctx, (const u32*)d_pairs, n, nbits, nb_from, nb_to, out);
+}
+
+static int rng_import_host(bmx_ctx* ctx, const void* ranges, int width, uint64_t n, uint64_t nbits, uint32_t nb_from, uint32_t nb_to,
+                           bmx_vec** out)
+{
+    int rc = set_dev(ctx); if (rc) return rc;
+    DevBuf d_pairs(ctx);
+    if (n) {
+        const size_t bytes = (size_t)n * 2u * (size_t)width;
+        if ((rc = dmalloc(ctx, &d_pairs.p, bytes))) return rc;
+        HIPCHK(hipMemcpyAsync(d_pairs.p, ranges, bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return rng_import(ctx, d_pairs.p, width, n, nbits, nb_from, nb_to, out);
+}
+
+// the maximal runs of ones as inclusive pairs (bmx_kernels14.h k_rng_ends_count / k_rs_scan / k_rng_expand)
+static int vec_ranges_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out, bool out_is_host, uint64_t cap, uint64_t* n)
+{
+    ARGCHK(ctx && v && v->ctx == ctx && n && (width == 4 || width == 8) && (cap == 0 || out));
+    int rc = set_dev(ctx); if (rc) return rc;
+    *n = 0;
+    const uint32_t nblocks = v->nblocks;
+    if (!nblocks) return BMX_OK;
+    if (width == 4 && (uint64_t)nblocks > 65536ull) { g_last_error = "32-bit positions cannot address this vector: use width 8"; return BMX_ERR_RANGE; }
+    DevBuf d_cs(ctx), d_ce(ctx), d_rs(ctx), d_re(ctx), host_out(ctx);
+    if ((rc = dmalloc(ctx, &d_cs.p, (size_t)nblocks * 4)) || (rc = dmalloc(ctx, &d_ce.p, (size_t)nblocks * 4)) ||
+        (rc = dmalloc(ctx, &d_rs.p, (size_t)nblocks * 8)) || (rc = dmalloc(ctx, &d_re.p, (size_t)nblocks * 8))) return rc;
+    const dim3 wgrid((nblocks + 3) / 4);
+    hipLaunchKernelGGL(k_rng_ends_count, wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)d_cs, (u32*)d_ce);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_cs, nblocks, (u64*)d_rs, ctx->d_small);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_ce, nblocks, (u64*)d_re, ctx->d_small + 1);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint64_t total = ctx->h_small[0];
+    if (ctx->h_small[1] != total) { g_last_error = "bmx_vec_to_ranges: starts and ends of the runs do not pair up"; return BMX_ERR_DEVICE; }
+    *n = total;
+    if (total > cap) { g_last_error = "output buffer too small for the intervals (n holds the number needed)"; return BMX_ERR_RANGE; }
+    if (!total) return BMX_OK;
+    const size_t bytes = (size_t)total * 2u * (size_t)width;
+    if (out_is_host && (rc = dmalloc(ctx, &host_out.p, bytes))) return rc;
+    void* d_out = out_is_host ? host_out.p : out;
+    if (width == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_expand<u64>), wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks,
+                                       (const u64*)d_rs, (const u64*)d_re, (u64*)d_out, total);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_expand<u32>), wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks,
+                            (const u64*)d_rs, (const u64*)d_re, (u32*)d_out, total);
+    KCHK();
+    if (out_is_host) HIPCHK(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BMX_OK;
+}
+
+extern "C" {
+
+int bmx_vec_from_ranges(bmx_ctx* ctx, const void* ranges, int width, uint64_t n, uint64_t nbits, bmx_vec** out)
+{ ABI_TRY
+    int rc = rng_args(ranges, width, n, nbits, out); if (rc) return rc;
+    *out = nullptr;
+    ARGCHK(ctx);
+    return rng_import_host(ctx, ranges, width, n, nbits, 0u, 0xFFFFFFFFu, out);
+ABI_END }
+
+int bmx_vec_from_ranges_dev(bmx_ctx* ctx, const void* d_ranges, int width, uint64_t n, uint64_t nbits, bmx_vec** out)
+{ ABI_TRY
+    int rc = rng_args(d_ranges, width, n, nbits, out); if (rc) return rc;
+    *out = nullptr;
+    ARGCHK(ctx);
+    if ((rc = set_dev(ctx))) return rc;
+    return rng_import(ctx, d_ranges, width, n, nbits, 0u, 0xFFFFFFFFu, out);
+ABI_END }
+
+int bmx_vec_from_ranges_shard(bmx_ctx* ctx, const void* ranges, int width, uint64_t n, uint64_t nbits,
+                              uint32_t nb_from, uint32_t nb_to, bmx_vec** out)
+{ ABI_TRY
+    int rc = rng_args(ranges, width, n, nbits, out); if (rc) return rc;
+    *out = nullptr;
+    ARGCHK(ctx);
+    return rng_import_host(ctx, ranges, width, n, nbits, nb_from, nb_to, out);
+ABI_END }
+
+int bmx_vec_to_ranges(bmx_ctx* ctx, const bmx_vec* v, int width, void* out, uint64_t cap, uint64_t* n)
+{ ABI_TRY
+    return vec_ranges_impl(ctx, v, width, out, true, cap, n);
+ABI_END }
+
+int bmx_vec_to_ranges_dev(bmx_ctx* ctx, const bmx_vec* v, int width, void* d_out, uint64_t cap, uint64_t* n)
+{ ABI_TRY
+    return vec_ranges_impl(ctx, v, width, d_out, false, cap, n);
 ABI_END }
 
 } // extern "C"

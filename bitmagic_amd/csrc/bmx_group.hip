@@ -519,6 +519,33 @@ int bmx_gvec_from_indices(bmx_group* g, const void* ids, int width, uint64_t n, 
     return BMX_OK;
 ABI_END }
 
+int bmx_gvec_from_ranges(bmx_group* g, const void* ranges, int width, uint64_t n, uint64_t nbits, bmx_gvec** out)
+{ ABI_TRY
+    ARGCHK(width == 4 || width == 8);
+    ARGCHK(n == 0 || ranges);
+    ARGCHK(out);
+    const uint64_t limit = 65536ull * 16 * BMX_BLOCK_BITS;
+    if (n > 0xFFFFFFFFull) { bmx_set_last_error("more than 2^32 - 1 pairs in one call"); return BMX_ERR_RANGE; }
+    if (nbits > limit) { bmx_set_last_error("vector too long"); return BMX_ERR_RANGE; }
+    ARGCHK(g);
+    *out = nullptr;
+    // the size of the single form: the members cut the same vector (either end of a pair may be the larger one)
+    uint64_t max_end = 0;
+    if (width == 8) { const uint64_t* p = (const uint64_t*)ranges; for (uint64_t i = 0; i < 2 * n; ++i) max_end = std::max(max_end, p[i]); }
+    else { const uint32_t* p = (const uint32_t*)ranges; for (uint64_t i = 0; i < 2 * n; ++i) max_end = std::max<uint64_t>(max_end, p[i]); }
+    if (n && max_end >= limit) { bmx_set_last_error("vector too long"); return BMX_ERR_RANGE; }
+    if (n) nbits = std::max<uint64_t>(nbits, max_end + 1);
+    const uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    GOwned<bmx_gvec> v = gvec_new(g, nbits, (uint32_t)nblocks64);
+    int rc = for_each_member(g, [&](int m) -> int {
+        uint32_t lo, hi; shard_of(v.get(), m, &lo, &hi);
+        return bmx_vec_from_ranges_shard(g->ctx[(size_t)m], ranges, width, n, nbits, lo, hi, &v->shard[(size_t)m]);
+    });
+    if (rc) return rc;
+    *out = v.release();
+    return BMX_OK;
+ABI_END }
+
 int bmx_gvec_info(const bmx_gvec* v, uint64_t* nbits, uint32_t* nblocks, uint32_t counts[4],
                   uint32_t* bit_slab_blocks, uint64_t* gap_words)
 { ABI_TRY

@@ -264,6 +264,18 @@ void k_ids_scatter_lds(const T* __restrict__ ids, u64 n, u64 per, u32 blk0, u32 
 // the GAP writer of k_emit_blocks (bmx_kernels.h; bit_block_to_gap, src/bmfunc.h:5542) for block b whose stats are *s: 16-byte
 // aligned at g, level bits of gap_calc_level, 0xFFFF padding; *d = its descriptor.  (k_emit_blocks keeps its own copy: calling
 // this one from it moved its register allocation.)
+// the header, the closing run end, the padding and the descriptor of a GAP block of len runs whose run ends are in g[1 .. len - 1]
+__device__ __forceinline__ void gap_close(u16* g, u32 len, u32 first, u64* d, u32 lane)
+{
+    if (lane == 0) {
+        const u32 level = len <= 124u ? 0u : len <= 252u ? 1u : len <= 508u ? 2u : 3u;   // gap_calc_level src/bmfunc.h:5418
+        g[0] = (u16)((len << 3) | (level << 1) | first);
+        g[len] = 65535u;
+        *d = DESC_MAKE_GAP(g, len, first);
+    }
+    if (lane >= 1u && lane <= 7u && len + lane < ((len + 1u + 7u) & ~7u)) g[len + lane] = 0xFFFFu;
+}
+
 __device__ __forceinline__ void gap_write_from_blk(const Blk& b, const BlockStat* s, u16* g, u64* d, u32 lane)
 {
     Blk t;
@@ -287,13 +299,7 @@ __device__ __forceinline__ void gap_write_from_blk(const Blk& b, const BlockStat
         }
         idx_base += __shfl(incl, 63, 64);
     }
-    if (lane == 0) {
-        const u32 level = len <= 124u ? 0u : len <= 252u ? 1u : len <= 508u ? 2u : 3u;   // gap_calc_level src/bmfunc.h:5418
-        g[0] = (u16)((len << 3) | (level << 1) | s->first);
-        g[len] = 65535u;
-        *d = DESC_MAKE_GAP(g, len, s->first);
-    }
-    if (lane >= 1u && lane <= 7u && len + lane < ((len + 1u + 7u) & ~7u)) g[len + lane] = 0xFFFFu;
+    gap_close(g, len, s->first, d, lane);
 }
 
 // the 8 KiB image of one touched block in this wave's LDS: its ids [beg, end) ORed in (loads issued 8 per lane at a time)

@@ -146,6 +146,28 @@ int bmx_vec_from_indices_dev(bmx_ctx* ctx, const void* d_ids, int width, uint64_
 /* blocks [nb_from, nb_to) of the vector above, rebased like bmx_vec_generate_shard; ids outside the range are dropped */
 int bmx_vec_from_indices_shard(bmx_ctx* ctx, const void* ids, int width, uint64_t n, int sort_order, uint64_t nbits,
                                uint32_t nb_from, uint32_t nb_to, int optimize, bmx_vec** out);
+/* ---- vectors from lists of intervals, and back ---- */
+/* bvector::set_range(left, right) (src/bm.h:2398; clear_range :2383, keep_range :7908) for every pair on an empty vector of
+ * nbits bits, then optimize(opt_compress).  ranges: n pairs stored interleaved l0, r0, l1, r1, ... (a contiguous (n, 2) array),
+ * elements of width 4 (uint32_t) or 8 (uint64_t) bytes, both ends inclusive.  A pair with right < left is swapped
+ * (src/bm.h:2407); pairs may come in any order, overlap, nest, touch or repeat.  The vector has max(nbits, largest end + 1) bits,
+ * at most 2^20 blocks and n < 2^32 (else BMX_ERR_RANGE; lists that are not sorted and separated: n < 2^31).  The table is the
+ * optimised one: untouched blocks NULL, wholly covered blocks FULL, the rest GAP below 1,276 runs, else a bit-block (the rule of
+ * bmx_vec_import_bits); it does not depend on the order of the pairs.  Whether the list is sorted and separated
+ * (l[i] >= r[i-1] + 2) is checked on the device and selects the path.  Device memory and time follow n and the blocks of the
+ * vector, never the covered bits.  _dev: the pairs are device memory, ready on the context's stream (bmx_vec_to_ranges_dev's
+ * output, a framework's tensor). */
+int bmx_vec_from_ranges(bmx_ctx* ctx, const void* ranges, int width, uint64_t n, uint64_t nbits, bmx_vec** out);
+int bmx_vec_from_ranges_dev(bmx_ctx* ctx, const void* d_ranges, int width, uint64_t n, uint64_t nbits, bmx_vec** out);
+/* blocks [nb_from, nb_to) of the vector above, rebased like bmx_vec_from_indices_shard; pairs are clipped to the range */
+int bmx_vec_from_ranges_shard(bmx_ctx* ctx, const void* ranges, int width, uint64_t n, uint64_t nbits,
+                              uint32_t nb_from, uint32_t nb_to, bmx_vec** out);
+/* The vector as the maximal runs of its ones, ascending, as inclusive pairs l0, r0, l1, r1, ...: what a
+ * bm::interval_enumerator<BV> loop yields (src/bmintervals.h:52-226; is_interval :248).  A run that crosses block borders is
+ * one pair.  width = 4 (vectors of <= 2^32 bits) or 8.  *n = number of intervals; when it exceeds cap nothing is written and
+ * BMX_ERR_RANGE is returned (call again with a buffer of *n pairs).  _dev: the buffer is device memory. */
+int bmx_vec_to_ranges(bmx_ctx* ctx, const bmx_vec* v, int width, void* out, uint64_t cap, uint64_t* n);
+int bmx_vec_to_ranges_dev(bmx_ctx* ctx, const bmx_vec* v, int width, void* d_out, uint64_t cap, uint64_t* n);
 /* bvector::calc_stat (src/bm.h:4010): counts[kind]; bit_slab_blocks / gap_words =
  * sizes (8 KiB blocks / uint16 words) of the two slabs bmx_vec_download fills.
  * Result vectors keep one slab slot per block column, so bit_slab_blocks may
@@ -475,6 +497,9 @@ int bmx_gvec_generate(bmx_group* g, uint64_t seed, uint32_t vec_id, int with_com
  * its block range (bmx_vec_from_indices_shard) */
 int bmx_gvec_from_indices(bmx_group* g, const void* ids, int width, uint64_t n, int sort_order,
                           uint64_t nbits, int optimize, bmx_gvec** out);
+/* bmx_vec_from_ranges (bvector::set_range, src/bm.h:2398) for a group: sized as the single form, cut at the group's partition in
+ * force; every member imports the pairs clipped to its block range (bmx_vec_from_ranges_shard) */
+int bmx_gvec_from_ranges(bmx_group* g, const void* ranges, int width, uint64_t n, uint64_t nbits, bmx_gvec** out);
 int bmx_gvec_free(bmx_group* g, bmx_gvec* v);
 /* totals over the shards; bit_slab_blocks / gap_words size the buffers of bmx_gvec_download */
 int bmx_gvec_info(const bmx_gvec* v, uint64_t* nbits, uint32_t* nblocks, uint32_t counts[4],

@@ -168,6 +168,37 @@ public:
         bvector imp(*ctx_); imp.adopt(r);
         op2(BMX_OR, imp, opt_flag ? opt_compress : opt_none);
     }
+    /// bvector<>::set_range(left, right, value)  src/bm.h:2398: the bits of [left, right] (both inclusive; swapped when
+    /// right < left, :2407) set or cleared: bmx_vec_from_ranges of the one pair, then bmx_op2 OR / SUB
+    bvector& set_range(size_type left, size_type right, bool value = true) { combine_range(value ? BMX_OR : BMX_SUB, left, right); return *this; }
+    /// bvector<>::clear_range(left, right)  src/bm.h:2383
+    void clear_range(size_type left, size_type right) { combine_range(BMX_SUB, left, right); }
+    /// bvector<>::keep_range(left, right)  src/bm.h:7908: everything outside [left, right] is cleared
+    void keep_range(size_type left, size_type right) { combine_range(BMX_AND, left, right); }
+    /// set_range for every pair {left, right} on an empty vector of nbits bits, then optimize() (bmx_vec_from_ranges)
+    void assign_ranges(const std::pair<size_type, size_type>* pairs, size_type n, size_type nbits = 0)
+    {
+        std::vector<size_type> flat; flat.reserve(2 * n);
+        for (size_type i = 0; i < n; ++i) { flat.push_back(pairs[i].first); flat.push_back(pairs[i].second); }
+        bmx_vec* r = nullptr;
+        check(bmx_vec_from_ranges(ctx_->handle(), flat.data(), 8, n, nbits, &r));
+        adopt(r);
+    }
+    /// the maximal runs of ones as inclusive {left, right} pairs, ascending (bmx_vec_to_ranges): what a
+    /// bm::interval_enumerator<BV> loop collects, src/bmintervals.h:52-226
+    void to_ranges(std::vector<std::pair<size_type, size_type>>& out) const
+    {
+        out.clear();
+        if (!h_) return;
+        uint64_t n = 0;
+        const int rc = bmx_vec_to_ranges(ctx_->handle(), h_, 8, nullptr, 0, &n);   // (the number of intervals first)
+        if (rc != BMX_OK && !(rc == BMX_ERR_RANGE && n)) check(rc);
+        if (!n) return;
+        std::vector<size_type> flat(2 * n);
+        check(bmx_vec_to_ranges(ctx_->handle(), h_, 8, flat.data(), n, &n));
+        out.reserve(n);
+        for (uint64_t i = 0; i < n; ++i) out.emplace_back(flat[2 * i], flat[2 * i + 1]);
+    }
     /// the sorted positions of the set bits (device compaction, bmx_vec_to_indices): what bm::bvector<>::enumerator or
     /// bm::for_each_bit would feed into a container, in one call
     void to_indices(std::vector<size_type>& out) const
@@ -310,6 +341,17 @@ private:
         if (!h_ && op != BMX_OR) return;                   // (src/bm.h:4176, 4220: nothing to keep or clear)
         bmx_vec* r = nullptr;
         check(bmx_vec_from_indices(ctx_->handle(), ids, width, n, so, size(), 0, &r));
+        if (!h_) { adopt(r); return; }
+        bvector imp(*ctx_); imp.adopt(r);
+        op2(op, imp, opt_none);
+    }
+    // this = this OP (the vector of the one range, as long as this one)
+    void combine_range(int op, size_type left, size_type right)
+    {
+        if (!h_ && op != BMX_OR) return;                   // nothing to clear or keep
+        const size_type pair[2] = {left, right};
+        bmx_vec* r = nullptr;
+        check(bmx_vec_from_ranges(ctx_->handle(), pair, 8, 1, size(), &r));
         if (!h_) { adopt(r); return; }
         bvector imp(*ctx_); imp.adopt(r);
         op2(op, imp, opt_none);

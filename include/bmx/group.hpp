@@ -110,6 +110,16 @@ public:
         check(bmx_gvec_from_indices(grp_->handle(), ids, 4, n, so, nbits, optimize, &h));
         adopt(h);
     }
+    /// bvector<>::set_range for every pair {left, right} on an empty vector of nbits bits, optimised, for the group
+    /// (bmx_gvec_from_ranges)
+    void assign_ranges(const std::pair<size_type, size_type>* pairs, size_type n, size_type nbits = 0)
+    {
+        std::vector<size_type> flat; flat.reserve(2 * n);
+        for (size_type i = 0; i < n; ++i) { flat.push_back(pairs[i].first); flat.push_back(pairs[i].second); }
+        bmx_gvec* h = nullptr;
+        check(bmx_gvec_from_ranges(grp_->handle(), flat.data(), 8, n, nbits, &h));
+        adopt(h);
+    }
     size_type size() const { uint64_t n = 0; if (h_) check(bmx_gvec_info(h_, &n, nullptr, nullptr, nullptr, nullptr)); return n; }
     uint32_t block_count() const { uint32_t n = 0; if (h_) check(bmx_gvec_info(h_, nullptr, &n, nullptr, nullptr, nullptr)); return n; }
     void calc_stat(bvector::statistics* st) const
