@@ -45,7 +45,7 @@ ID_MAX64 = 0xFFFFFFFFFFFFFFFF
 # bm::sort_order (src/bmconst.h:204-210): what the caller knows about the order of an id list
 BM_UNSORTED, BM_SORTED, BM_SORTED_UNIFORM, BM_UNKNOWN = 0, 1, 2, 3
 
-__all__ = ["context", "bvector", "aggregator", "slice_scanner", "rs_index", "group", "gbvector", "gaggregator", "gpipeline", "bit_import_u32", "count_and", "count_or",
+__all__ = ["context", "bvector", "aggregator", "slice_scanner", "rs_index", "rank_compressor", "group", "gbvector", "gaggregator", "gpipeline", "bit_import_u32", "count_and", "count_or",
            "count_xor", "count_sub", "distance_operation", "distance_matrix", "distance_matrix_dev",
            "COUNT_AND", "COUNT_XOR", "COUNT_OR", "COUNT_SUB_AB", "COUNT_SUB_BA", "COUNT_A", "COUNT_B", "BmxError", "simd_version", "device_count", "agg_run_options",
            "agg_opt_only_counts", "agg_opt_bvect_and_counts", "agg_opt_disable_bvects_and_counts",
@@ -504,6 +504,49 @@ class rs_index:
         if n:
             check(lib().bmx_rs_export(self.ctx._h, self._h, _ptr(bc), _ptr(sub)))
         return bc, sub
+
+
+class rank_compressor:
+    """bm::rank_compressor<BV> (src/bmalgo.h:452-707) on the device: whole vectors between the row space and the rank space of
+    an index vector.  compress: bit r of the result is set iff the r-th one of bv_idx is set in bv_src (count(bv_idx) bits;
+    bits of bv_src outside bv_idx are ignored).  decompress: the inverse (bv_idx's size; bits of bv_src at or beyond
+    count(bv_idx) are ignored).  rs_idx: bv_idx's rs_index, or None (one count pass instead).  optimize=False leaves every
+    non-empty block a bit-block; True applies the rule of bit_import_u32."""
+
+    def __init__(self, ctx: context):
+        self.ctx = ctx
+
+    def _one(self, fn, bv_idx: bvector, rs_idx, bv_src: bvector, optimize: bool) -> bvector:
+        h = C.c_void_p()
+        check(fn(self.ctx._h, bv_idx._h, rs_idx._h if rs_idx is not None else None, bv_src._h, int(bool(optimize)), C.byref(h)))
+        return bvector(self.ctx, h)
+
+    def _many(self, fn, bv_idx: bvector, srcs, rs_idx, optimize: bool) -> list:
+        srcs = list(srcs)
+        n = len(srcs)
+        if not n:
+            return []
+        arr = (C.c_void_p * n)(*[(v._h if v is not None else None) for v in srcs])
+        outs = (C.c_void_p * n)()
+        check(fn(self.ctx._h, bv_idx._h, rs_idx._h if rs_idx is not None else None, arr, n, int(bool(optimize)), outs))
+        return [bvector(self.ctx, C.c_void_p(outs[i])) if outs[i] else None for i in range(n)]
+
+    def compress(self, bv_idx: bvector, bv_src: bvector, optimize: bool = False) -> bvector:                  # :497
+        return self._one(lib().bmx_rank_compress, bv_idx, None, bv_src, optimize)
+
+    def decompress(self, bv_idx: bvector, bv_src: bvector, rs_idx: "rs_index | None" = None, optimize: bool = False) -> bvector:   # :571
+        return self._one(lib().bmx_rank_decompress, bv_idx, rs_idx, bv_src, optimize)
+
+    def compress_by_source(self, bv_idx: bvector, rs_idx: "rs_index | None", bv_src: bvector, optimize: bool = False) -> bvector:  # :625
+        return self._one(lib().bmx_rank_compress, bv_idx, rs_idx, bv_src, optimize)
+
+    def compress_many(self, bv_idx: bvector, srcs, rs_idx: "rs_index | None" = None, optimize: bool = False) -> list:
+        """rsc_sparse_vector::load_from (src/bmsparsevec_compr.h:1496): every plane (None = absent -> None) against one index"""
+        return self._many(lib().bmx_rank_compress_many, bv_idx, srcs, rs_idx, optimize)
+
+    def decompress_many(self, bv_idx: bvector, srcs, rs_idx: "rs_index | None" = None, optimize: bool = False) -> list:
+        """rsc_sparse_vector::load_to (src/bmsparsevec_compr.h:1532)"""
+        return self._many(lib().bmx_rank_decompress_many, bv_idx, srcs, rs_idx, optimize)
 
 
 def bit_import_u32(ctx: context, words, optimize: bool = True) -> bvector:
@@ -1009,6 +1052,13 @@ class slice_scanner:
             return pipe.get_or_target()
         return acc if acc is not None else self._compare(CMP_GT, (1 << 64) - 1)       # nothing to look for: empty result
 
+    def decompress(self, bv: "bvector", rs_idx: "rs_index | None" = None) -> "bvector":
+        """scanner.decompress(sv, bv)  src/bmsparsevec_algo.h:4525: a result in the rank space of a compressed container back to its
+        rows through the NOT-NULL vector; without one the argument is the answer"""
+        if self.not_null is None:
+            return bv
+        return rank_compressor(self.ctx).decompress(self.not_null, bv, rs_idx)
+
     def invert(self, bv: "bvector") -> "bvector":
         """scanner.invert(sv, bv)  src/bmsparsevec_algo.h:2321: the other rows of [0, size), NULL rows excluded"""
         zero_planes = slice_scanner(self.ctx, [], size=self.size(), not_null=self.not_null)
@@ -1471,6 +1521,12 @@ class gslice_scanner(slice_scanner):
         if self._size is None:
             self._size = max([p.info()["nbits"] for p in self.slices if p is not None], default=0)
         return self._size
+
+    def decompress(self, bv, rs_idx=None):
+        """rank space does not respect the block-range cut of a group: no sharded twin (include/bmx.h, bmx_rank_decompress)"""
+        if self.not_null is None:
+            return bv
+        raise NotImplementedError("rank_compressor has no group form")
 
     def _new_pipeline(self):
         return gpipeline(self.grp)

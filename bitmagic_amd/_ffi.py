@@ -120,6 +120,10 @@ def lib() -> C.CDLL:
         "bmx_select_batch": (i32, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
         "bmx_rank_batch_dev": (i32, [vp, vp, vp, vp, C.c_size_t, vp]),
         "bmx_select_batch_dev": (i32, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
+        "bmx_rank_compress": (i32, [vp, vp, vp, vp, i32, P(vp)]),
+        "bmx_rank_decompress": (i32, [vp, vp, vp, vp, i32, P(vp)]),
+        "bmx_rank_compress_many": (i32, [vp, vp, vp, P(vp), C.c_size_t, i32, P(vp)]),
+        "bmx_rank_decompress_many": (i32, [vp, vp, vp, P(vp), C.c_size_t, i32, P(vp)]),
         "bmx_group_create": (i32, [P(i32), i32, i32, P(vp)]),
         "bmx_group_destroy": (i32, [vp]),
         "bmx_group_size": (i32, [vp, P(i32)]),

@@ -17,6 +17,7 @@
 #include "bmx_kernels12.h"
 #include "bmx_kernels13.h"
 #include "bmx_kernels14.h"
+#include "bmx_kernels15.h"
 
 #include <algorithm>
 #include <atomic>
@@ -885,6 +886,7 @@ static int ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
     else if (k == "rs_select_top") { ARGCHK(value >= -1 && value <= 1); ctx->rs_select_top = value; }
     else if (k == "rs_lanes") { ARGCHK(value == 0 || value == 2 || value == 4 || value == 8); ctx->rs_lanes = value; }
     else if (k == "pipe_wg") { ARGCHK(value == 0 || (value >= 64 && value <= 1024 && value % 64 == 0)); ctx->pipe_wg = value; }
+    else if (k == "rankc_path") { ARGCHK(value >= -1 && value <= 1); ctx->rankc_path = value; }
     else if (k == "xcd_swizzle") ctx->xcd_swz = value != 0;
     else { g_last_error = "unknown tuning key"; return BMX_ERR_BADARG; }
     return BMX_OK;
@@ -1030,7 +1032,7 @@ int bmx_ctx_create(int device, void* stream, bmx_ctx** out)
     // an invalid value is ignored (the default stays)
     static const char* const env_keys[][2] = {
         {"BMX_PIPE_UNROLL", "pipe_unroll"}, {"BMX_PIPE_ROWS", "pipe_rows"}, {"BMX_PIPE_NT", "pipe_nt"},
-        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}};
+        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}};
     for (auto& kv : env_keys)
         if (const char* e = getenv(kv[0])) (void)ctx_set_tuning(ctx.get(), kv[1], atoi(e));
     g_last_error.clear();
@@ -4390,6 +4392,179 @@ int bmx_select_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uin
     buf.reset();
     if (e != hipSuccess) return fail_hip(e, "bmx_select_batch", __LINE__);
     return rc;
+ABI_END }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------
+// bm::rank_compressor (src/bmalgo.h:452-707; bmx_kernels15.h): n sources against one index, dir 0 = compress, 1 = decompress
+// ---------------------------------------------------------------------------
+static int rankc_empty(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, bmx_vec** out)
+{
+    int rc;
+    Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
+    if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
+    if (nblocks) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nblocks * 8, ctx->stream));
+    v->counts[BMX_NULL] = nblocks;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *out = v.release();
+    return BMX_OK;
+}
+
+static int rankc_run(bmx_ctx* ctx, int dir, const bmx_vec* idx, const bmx_rs* rs, const bmx_vec* const* srcs, size_t n, int optimize,
+                     bmx_vec** outs)
+{
+    ARGCHK(outs || n == 0);
+    for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    ARGCHK(ctx && idx && idx->ctx == ctx && (n == 0 || srcs));
+    ARGCHK(!rs || (rs->ctx == ctx && rs->nblocks == idx->nblocks));
+    for (size_t i = 0; i < n; ++i) ARGCHK(!srcs[i] || srcs[i]->ctx == ctx);
+    if (n > 65535) { g_last_error = "more than 65,535 sources in one call"; return BMX_ERR_RANGE; }
+    if (idx->nblocks > IDS_MAX_BLOCKS) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    int rc = set_dev(ctx); if (rc) return rc;
+    if (!n) return BMX_OK;
+    const uint32_t inb = idx->nblocks;
+    // 1. the ones of idx up to and including every block: the index's running counts, or one count pass into scratch
+    DevBuf d_bc(ctx), d_rc(ctx);
+    const u64* P = nullptr; uint64_t total = 0;
+    if (rs) { P = rs->d_rcount; total = rs->count; }
+    else if (inb) {
+        if ((rc = dmalloc(ctx, &d_bc.p, (size_t)inb * 4)) || (rc = dmalloc(ctx, &d_rc.p, (size_t)inb * 8))) return rc;
+        hipLaunchKernelGGL(k_block_counts, dim3((inb + 3) / 4), dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, (u32*)d_bc);
+        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, inb, (u64*)d_rc, ctx->d_small);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        P = (const u64*)d_rc.p; total = ctx->h_small[0];
+        d_bc.reset();
+    }
+    const uint64_t nbits_out = dir == 0 ? total : idx->nbits;
+    const uint32_t nbt = dir == 0 ? (uint32_t)((total + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS) : inb;
+    // the results live here until all of them are complete: a failure frees every one
+    std::vector<Owned<bmx_vec>> res(n);
+    // 2. the sources that need computing (an absent plane yields none; the index itself under the same handle is copied,
+    //    src/bmalgo.h:505-509, 579-583: a rule on identity, not on content)
+    std::vector<RankcSrc> hs(n, RankcSrc{nullptr, 0u, 0u});
+    size_t live = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!srcs[i]) continue;
+        if (srcs[i] == idx) { bmx_vec* c = nullptr; if ((rc = vec_clone(ctx, idx, &c))) return rc; res[i].reset(c); continue; }
+        if (!total || !nbt) { bmx_vec* c = nullptr; if ((rc = rankc_empty(ctx, nbits_out, nbt, &c))) return rc; res[i].reset(c); continue; }
+        hs[i] = RankcSrc{srcs[i]->d_desc, srcs[i]->nblocks, 0u};
+        ++live;
+    }
+    if (live) {
+        DevBuf d_srcs(ctx);
+        if ((rc = dmalloc(ctx, &d_srcs.p, n * sizeof(RankcSrc))) || (rc = h2d_staged(ctx, d_srcs.p, hs.data(), n * sizeof(RankcSrc)))) return rc;
+        const RankcSrc* ds = (const RankcSrc*)d_srcs.p;
+        // rankc_path: 1 = whole blocks; 0 = ascending positions into the sorted path of from_indices.  Automatic: compress
+        // goes through positions where a target block is fed by more than 32 index blocks on average (the block kernel has
+        // one workgroup per target block); decompress has a wave per index block either way and stays with the blocks
+        const int path = ctx->rankc_path >= 0 ? ctx->rankc_path : (dir == 0 && total < (uint64_t)inb * 2048ull) ? 0 : 1;
+        if (path == 1) {
+            const size_t items = n * (size_t)nbt;
+            DevBuf d_st(ctx), d_offs(ctx), d_tot(ctx), d_outs(ctx);
+            if ((rc = dmalloc(ctx, &d_st.p, items * sizeof(BlockStat))) || (rc = dmalloc(ctx, &d_offs.p, items * 4)) ||
+                (rc = dmalloc(ctx, &d_tot.p, n * 8 * sizeof(u64))) || (rc = dmalloc(ctx, &d_outs.p, n * sizeof(RankcOut)))) return rc;
+            const dim3 dgrid((inb + 3) / 4, (u32)n), cgrid(nbt, (u32)n);
+            if (dir == 0) hipLaunchKernelGGL(k_rankc_cstats, cgrid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P, (u64)total, nbt,
+                                             ds, optimize, (BlockStat*)d_st);
+            else hipLaunchKernelGGL(k_rankc_dstats, dgrid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P, ds, optimize,
+                                    (BlockStat*)d_st, (u32*)nullptr);
+            KCHK();
+            for (size_t i = 0; i < n; ++i)
+                if (hs[i].desc) hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, (const BlockStat*)d_st + i * nbt, nbt,
+                                                   (u32*)d_offs + i * nbt, (u64*)d_tot + i * 8);
+            KCHK();
+            std::vector<u64> tot(n * 8, 0);
+            HIPCHK(hipMemcpyAsync(tot.data(), d_tot.p, n * 8 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            std::vector<RankcOut> ho(n, RankcOut{nullptr, nullptr, nullptr, 0ull});
+            for (size_t i = 0; i < n; ++i) {
+                if (!hs[i].desc) continue;
+                Owned<bmx_vec> v = vec_alloc_host(ctx, nbits_out, nbt);
+                for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)tot[i * 8 + 2 + k];
+                if ((rc = vec_alloc_device(v.get(), (uint32_t)tot[i * 8], tot[i * 8 + 1]))) return rc;
+                ho[i] = RankcOut{v->d_bits, v->d_gaps, v->d_desc, 0ull};
+                res[i] = std::move(v);
+            }
+            if ((rc = h2d_staged(ctx, d_outs.p, ho.data(), n * sizeof(RankcOut)))) return rc;
+            if (dir == 0) hipLaunchKernelGGL(k_rankc_cemit, cgrid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P, (u64)total, nbt,
+                                             ds, (const BlockStat*)d_st, (const u32*)d_offs, (const RankcOut*)d_outs);
+            else hipLaunchKernelGGL(k_rankc_demit, dgrid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P, ds,
+                                    (const BlockStat*)d_st, (const u32*)d_offs, (const RankcOut*)d_outs);
+            KCHK();
+            for (size_t i = 0; i < n; ++i) if (hs[i].desc && (rc = vec_build_tdir(ctx, res[i].get()))) return rc;
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+        } else {
+            // positions: the ones per (source, index block), their running counts per source, the lists, from_indices
+            const size_t items = n * (size_t)inb;
+            DevBuf d_cnt(ctx), d_run(ctx), d_tot(ctx), d_base(ctx), d_pos(ctx);
+            if ((rc = dmalloc(ctx, &d_cnt.p, items * 4)) || (rc = dmalloc(ctx, &d_run.p, items * 8)) ||
+                (rc = dmalloc(ctx, &d_tot.p, n * 8)) || (rc = dmalloc(ctx, &d_base.p, n * 8))) return rc;
+            const dim3 grid((inb + 3) / 4, (u32)n);
+            if (dir == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rankc_cpos<true>), grid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P,
+                                             ds, (u32*)d_cnt, (const u64*)nullptr, (const u64*)nullptr, (u64*)nullptr);
+            else hipLaunchKernelGGL(k_rankc_dstats, grid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P, ds, 0,
+                                    (BlockStat*)nullptr, (u32*)d_cnt);
+            KCHK();
+            HIPCHK(hipMemsetAsync(d_tot.p, 0, n * 8, ctx->stream));
+            for (size_t i = 0; i < n; ++i)
+                if (hs[i].desc) hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_cnt + i * inb, inb,
+                                                   (u64*)d_run + i * inb, (u64*)d_tot + i);
+            KCHK();
+            std::vector<u64> tot(n, 0), base(n, 0);
+            HIPCHK(hipMemcpyAsync(tot.data(), d_tot.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            d_cnt.reset();
+            u64 all = 0;
+            for (size_t i = 0; i < n; ++i) { base[i] = all; all += tot[i]; }
+            if (all) {
+                if ((rc = dmalloc(ctx, &d_pos.p, (size_t)all * 8)) || (rc = h2d_staged(ctx, d_base.p, base.data(), n * 8))) return rc;
+                if (dir == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rankc_cpos<false>), grid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb,
+                                                 P, ds, (u32*)nullptr, (const u64*)d_run, (const u64*)d_base, (u64*)d_pos);
+                else hipLaunchKernelGGL(k_rankc_dpos, grid, dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, P, ds,
+                                        (const u64*)d_run, (const u64*)d_base, (u64*)d_pos);
+                KCHK();
+            }
+            d_run.reset();
+            for (size_t i = 0; i < n; ++i) {
+                if (!hs[i].desc) continue;
+                if (tot[i] > 0xFFFFFFFFull) { g_last_error = "more than 2^32 - 1 ones in a result of the positions path"; return BMX_ERR_RANGE; }
+                bmx_vec* c = nullptr;
+                if ((rc = ids_import(ctx, (const u64*)d_pos.p + base[i], 8, tot[i], nbits_out, 0u, 0xFFFFFFFFu, optimize, &c))) return rc;
+                res[i].reset(c);
+            }
+        }
+    }
+    for (size_t i = 0; i < n; ++i) outs[i] = res[i].release();
+    return BMX_OK;
+}
+
+extern "C" {
+
+int bmx_rank_compress(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* src, int optimize, bmx_vec** out)
+{ ABI_TRY
+    ARGCHK(out); *out = nullptr; ARGCHK(src);
+    return rankc_run(ctx, 0, idx, rs_idx, &src, 1, optimize, out);
+ABI_END }
+
+int bmx_rank_decompress(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* src, int optimize, bmx_vec** out)
+{ ABI_TRY
+    ARGCHK(out); *out = nullptr; ARGCHK(src);
+    return rankc_run(ctx, 1, idx, rs_idx, &src, 1, optimize, out);
+ABI_END }
+
+int bmx_rank_compress_many(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* const* srcs, size_t n, int optimize,
+                           bmx_vec** outs)
+{ ABI_TRY
+    return rankc_run(ctx, 0, idx, rs_idx, srcs, n, optimize, outs);
+ABI_END }
+
+int bmx_rank_decompress_many(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* const* srcs, size_t n, int optimize,
+                             bmx_vec** outs)
+{ ABI_TRY
+    return rankc_run(ctx, 1, idx, rs_idx, srcs, n, optimize, outs);
 ABI_END }
 
 } // extern "C"

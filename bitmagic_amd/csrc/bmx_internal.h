@@ -124,6 +124,7 @@ struct bmx_ctx {
     int rs_select_sel = -1;    // select lines (k_select_sel: the ones' positions laid out 60 / 30 per 128-byte line, one line per query, no search): -1 = built where they cost <= 2 x the vector + its rank lines, 0 = never built / never used, 1 = always (16-bit offsets, 32-bit if a line spans >= 2^16 bits), 2 = always with 32-bit offsets
     int rs_sorted_hint = 0;    // the caller's select batches arrive with ascending ranks (enumeration): the shape that is fastest for them
     int rs_lanes = 0;          // rank: lanes per query (k_rank_l): 0 = automatic, 8 = the original kernel, 2, 4
+    int rankc_path = -1;       // rank_compressor (bmx_kernels15.h): -1 = automatic, 0 = ascending positions into the sorted path of from_indices, 1 = whole blocks
     int xcd_swz = 1;
 };
 

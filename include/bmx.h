@@ -88,7 +88,7 @@ int bmx_ctx_synchronize(bmx_ctx* ctx);
 /* launch-shape knobs of the counts pipeline (results never depend on them; 0 / -1 = automatic):
  * "pipe_rows" 0|8|4|2|1 (KiB of a block per work item), "pipe_unroll" 0|1|2|4|8|16, "pipe_nt" 0|1,
  * "pipe_wg" 0|64..1024 (multiples of 64; the default build carries 256, 384, 512, 640, 768), "pipe_staged" -1|0|1, "pipe_slots" 8|16,
- * "pipe_window" -1|0|N (block columns per launch), "pipe_split" -1|0|1, "direct_cols" 0..N (one-launch aggregation over small collections), "ff_window" -1|0|N (first launch window of find_first_and_sub), "pair_stream" -1|0|2|4|8 and "pair_wgs" 1..8 (shape of the streaming pairwise count kernel), "pair_loop" -1|0|1..5 and "pair_nt" 0|1 (persistent pairwise count kernel for mixed block kinds: workgroups per CU, non-temporal loads), "eq_big_shape" 0|1|2, "gap_count" -1|0|1 (counting formulation for GAP-only counts pipelines), "range_halves" 0|1 (comparison search in half-block passes), "rs_lanes" 0|2|4|8 (lanes per rank query), "rs_lines" 0|1|2 (build_rs_index also lays the vector out as rank lines: one 128-byte line per rank query), "rs_select_lines" 0|1|2 (select through the block index | the lines + octant directory | the select directory over the lines) and "rs_sdir_shift" 0|6..20 (log2 of the ones per select-directory entry; 0 = an entry per ~10 lines), "gap_pack" -1|0|1 (packed collections, see below), "eq_big" -1|0|1 (table form of bmx_slice_eq_counts), "op2_wgs" 1..8 and "op2_nt" 0..3 (streaming bit_and/or/xor/sub kernel: workgroups per CU; bit 0 / 1 = non-temporal loads / stores), "op2_loop" -1|0|1..8 (persistent bit_and/or/xor/sub kernel for mixed block kinds: workgroups per CU), "or_rows" -1|0|1 and "or_depth" 4|8 (combine_or over >= 64 sparse GAP-only operands through the vectors' tile directories: automatic | never | always; rows in flight per wave), "coll_members" -1|0|1 (lists that are SOME vectors of a prepared collection: the member directory automatic | never | whenever covered), "or_tile" 0..3, "xcd_swizzle" 0|1.  Environment twins (BMX_PIPE_ROWS, ...) pass the same checks. */
+ * "pipe_window" -1|0|N (block columns per launch), "pipe_split" -1|0|1, "direct_cols" 0..N (one-launch aggregation over small collections), "ff_window" -1|0|N (first launch window of find_first_and_sub), "pair_stream" -1|0|2|4|8 and "pair_wgs" 1..8 (shape of the streaming pairwise count kernel), "pair_loop" -1|0|1..5 and "pair_nt" 0|1 (persistent pairwise count kernel for mixed block kinds: workgroups per CU, non-temporal loads), "eq_big_shape" 0|1|2, "gap_count" -1|0|1 (counting formulation for GAP-only counts pipelines), "range_halves" 0|1 (comparison search in half-block passes), "rs_lanes" 0|2|4|8 (lanes per rank query), "rs_lines" 0|1|2 (build_rs_index also lays the vector out as rank lines: one 128-byte line per rank query), "rs_select_lines" 0|1|2 (select through the block index | the lines + octant directory | the select directory over the lines) and "rs_sdir_shift" 0|6..20 (log2 of the ones per select-directory entry; 0 = an entry per ~10 lines), "gap_pack" -1|0|1 (packed collections, see below), "eq_big" -1|0|1 (table form of bmx_slice_eq_counts), "op2_wgs" 1..8 and "op2_nt" 0..3 (streaming bit_and/or/xor/sub kernel: workgroups per CU; bit 0 / 1 = non-temporal loads / stores), "op2_loop" -1|0|1..8 (persistent bit_and/or/xor/sub kernel for mixed block kinds: workgroups per CU), "or_rows" -1|0|1 and "or_depth" 4|8 (combine_or over >= 64 sparse GAP-only operands through the vectors' tile directories: automatic | never | always; rows in flight per wave), "coll_members" -1|0|1 (lists that are SOME vectors of a prepared collection: the member directory automatic | never | whenever covered), "or_tile" 0..3, "xcd_swizzle" 0|1, "rankc_path" -1|0|1 (bmx_rank_compress / bmx_rank_decompress: automatic | ascending positions into the sorted path of bmx_vec_from_indices | whole blocks; results never depend on it).  Environment twins (BMX_PIPE_ROWS, ...) pass the same checks. */
 int bmx_ctx_set_tuning(bmx_ctx* ctx, const char* key, int value);
 /* The context keeps freed device blocks in a size-keyed cache (results of same-shaped
  * operations re-use them instead of paying hipMalloc/hipFree, which synchronises the
@@ -443,6 +443,37 @@ int bmx_rank_batch_dev(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs,
                        const uint64_t* d_n, size_t q, uint64_t* d_out);
 int bmx_select_batch_dev(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs,
                          const uint64_t* d_rank, size_t q, uint64_t* d_pos, uint8_t* d_found);
+
+/* ---- bm::rank_compressor (src/bmalgo.h:452-707): whole vectors between the row space and the rank space of idx ----
+ * compress   (:497 compress, :625 compress_by_source): bit r of *out is set iff the r-th one of idx (0-based) is set in src.
+ *            *out has count(idx) bits (possibly 0), as rsc_sparse_vector::load_from resizes it (src/bmsparsevec_compr.h:1496).
+ *            Bits of src outside idx are ignored: the result is that of src & idx (the reference only asserts the subset,
+ *            :526-527; this is the defined extension).
+ * decompress (:571): bit p of *out is set iff p is a one of idx and bit rank_idx(p) - 1 of src is set.  *out has idx's bits
+ *            and block count.  Bits of src at positions >= count(idx) are ignored (the reference's loop ends with the index
+ *            enumerator, :593).
+ * rs_idx     the rank-select index of idx (the reference's rs_idx of decompress, bc_idx of compress_by_source), or NULL: only
+ *            its running count per block is used, and with NULL the library computes that with one count pass into scratch
+ *            (no full index is built).  An index of another context, or whose block count differs from idx's:
+ *            BMX_ERR_BADARG.
+ * idx and src may hold any block kinds and differ in length (missing blocks are NULL).  idx == src (the same HANDLE): *out is
+ * a block-for-block copy of src, the reference's pointer rule (:505-509, :579-583) -- a rule on identity, not on content: an
+ * equal vector under another handle is computed.
+ * optimize == 0: every target block that receives a bit is a bit-block (what bv_target.set(ibuffer, n, BM_SORTED) leaves);
+ * optimize != 0: the rule of bmx_vec_import_bits (FULL, GAP below 1,276 runs, else a bit-block).  A block that receives no
+ * bit is NULL in both.  The table is laid out as bmx_vec_import_bits lays it out: byte-identical to bmx_vec_to_indices ->
+ * bmx_rank_batch / bmx_select_batch -> bmx_vec_from_indices(BMX_SORTED).
+ * _many: n sources against one index (load_from / load_to, src/bmsparsevec_compr.h:1496-1541); a NULL entry (an absent plane)
+ * yields a NULL output; outs[i] equals the single call on srcs[i]; the index prefix is computed once and the kernels run over
+ * (source, block) pairs.  On any failure every output already built is freed and all outs[] are NULL.
+ * At most 2^20 blocks (BMX_ERR_RANGE) and 65,535 sources.  No group (bmx_g*) twins: rank space does not respect the
+ * block-range cut.  No bmx_pending operands. */
+int bmx_rank_compress(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* src, int optimize, bmx_vec** out);
+int bmx_rank_decompress(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* src, int optimize, bmx_vec** out);
+int bmx_rank_compress_many(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* const* srcs, size_t n,
+                           int optimize, bmx_vec** outs);
+int bmx_rank_decompress_many(bmx_ctx* ctx, const bmx_vec* idx, const bmx_rs* rs_idx, const bmx_vec* const* srcs, size_t n,
+                             int optimize, bmx_vec** outs);
 
 /* ---- multi-GPU: device groups (SURVEY.md section 8(b) "init with a device list", section 8(e)) ----
  * Every block column (i,j) is independent for AND/OR/XOR/SUB/COUNT (src/bmaggregator.h:1113-1121,1184-1218,

@@ -750,3 +750,5 @@ private:
 };
 
 } // namespace bmx
+
+#include "rank_compressor.hpp"
