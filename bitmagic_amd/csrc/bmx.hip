@@ -1292,6 +1292,53 @@ static int vec_build_tdir(bmx_ctx* ctx, bmx_vec* v)
     return BMX_OK;
 }
 
+// ---- the tail every creation path shares: stats into BlockStat (the caller's kernel), layout_read, vec_alloc_device, the
+// caller's emit pass, vec_build_tdir, a synchronise, release(); vec_all_null where there is nothing to emit ----
+// what k_scan_layout leaves in its result words: bit-block slots, GAP words (padded), blocks of each kind
+struct Layout {
+    uint32_t n_bit = 0; uint64_t gap_words = 0; uint32_t counts[4] = {0, 0, 0, 0};
+    Layout() {}
+    explicit Layout(const u64* w) : n_bit((uint32_t)w[0]), gap_words(w[1]) { for (int k = 0; k < 4; ++k) counts[k] = (uint32_t)w[2 + k]; }
+};
+// the layout scan over st[0 .. nblocks) into offs[], and its totals on the host (synchronises)
+static int layout_read(bmx_ctx* ctx, const BlockStat* st, uint32_t nblocks, u32* offs, Layout* lay)
+{
+    hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, st, nblocks, offs, ctx->d_small);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *lay = Layout(ctx->h_small);
+    return BMX_OK;
+}
+
+// a vector of nblocks NULL blocks: descriptors and the two minimal slabs of vec_alloc_device, nothing else (synchronises)
+static int vec_all_null(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, bmx_vec** out)
+{
+    int rc;
+    Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
+    if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
+    if (nblocks) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nblocks * 8, ctx->stream));
+    v->counts[BMX_NULL] = nblocks;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *out = v.release();
+    return BMX_OK;
+}
+
+// does the vector hold anything but NULL blocks?  (what `any` / `found` report, and what keeps a group's result)
+static bool vec_any_block(const bmx_vec* v) { return (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0; }
+
+// blocks [nb_from, nb_to) of a vector of nbits bits: nb_to clamped to the vector, and the bits the shard holds
+struct ShardWindow { uint32_t nblocks; uint64_t bits; };
+static int shard_window(uint64_t nbits, uint32_t nb_from, uint32_t nb_to, ShardWindow* w)
+{
+    const uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nb_to > nblocks64) nb_to = (uint32_t)nblocks64;
+    if (nb_from > nb_to) { g_last_error = "nb_from > nb_to"; return BMX_ERR_RANGE; }
+    const uint64_t lo = (uint64_t)nb_from * BMX_BLOCK_BITS, hi = std::min<uint64_t>(nbits, (uint64_t)nb_to * BMX_BLOCK_BITS);
+    *w = ShardWindow{nb_to - nb_from, hi > lo ? hi - lo : 0};
+    return BMX_OK;
+}
+
 int bmx_vec_free(bmx_ctx* ctx, bmx_vec* v) { ABI_TRY if (!v) return BMX_OK; ARGCHK(ctx && v->ctx == ctx); return vec_release(v); ABI_END }
 
 int bmx_vec_upload(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks,
@@ -1372,17 +1419,14 @@ static int vec_from_raw(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, int opti
     u32* offs = (u32*)((char*)ctx->aux + (size_t)nblocks * sizeof(BlockStat));
     const uint4* raw = (const uint4*)ctx->scratch;
     Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
+    Layout lay;
     if (nblocks) {
         hipLaunchKernelGGL(k_block_stats, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, raw, nblocks, optimize, st);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, st, nblocks, offs, ctx->d_small);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    } else memset(ctx->h_small, 0, 6 * sizeof(u64));
-    uint32_t n_bit = (uint32_t)ctx->h_small[0]; uint64_t gap_words = ctx->h_small[1];
-    for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
-    if ((rc = vec_alloc_device(v.get(), n_bit, gap_words))) return rc;
+        if ((rc = layout_read(ctx, st, nblocks, offs, &lay))) return rc;
+    }
+    memcpy(v->counts, lay.counts, sizeof(v->counts));
+    if ((rc = vec_alloc_device(v.get(), lay.n_bit, lay.gap_words))) return rc;
     if (nblocks) {
         hipLaunchKernelGGL(k_emit_blocks, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                            raw, nblocks, st, offs, v->d_bits, v->d_gaps, v->d_desc);
@@ -1417,13 +1461,10 @@ int bmx_vec_generate_shard(bmx_ctx* ctx, uint64_t seed, uint32_t vec_id, int wit
     ARGCHK(ctx && out && density_q16 <= 65536u);
     *out = nullptr;
     int rc = set_dev(ctx); if (rc) return rc;
-    uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    if (nb_to > nblocks64) nb_to = (uint32_t)nblocks64;
-    if (nb_from > nb_to) { g_last_error = "nb_from > nb_to"; return BMX_ERR_RANGE; }
-    uint32_t nblocks = nb_to - nb_from;
-    uint64_t lo = (uint64_t)nb_from * BMX_BLOCK_BITS, hi = std::min<uint64_t>(nbits, (uint64_t)nb_to * BMX_BLOCK_BITS);
-    uint64_t shard_bits = hi > lo ? hi - lo : 0;
+    if (nbits > 65536ull * 16 * BMX_BLOCK_BITS) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    ShardWindow win;
+    if ((rc = shard_window(nbits, nb_from, nb_to, &win))) return rc;
+    const uint32_t nblocks = win.nblocks;
     size_t raw_bytes = (size_t)nblocks * 8192;
     if ((rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, std::max<size_t>(raw_bytes, 8192)))) return rc;
     u64 nwords64 = (u64)nblocks * 1024u;
@@ -1433,7 +1474,7 @@ int bmx_vec_generate_shard(bmx_ctx* ctx, uint64_t seed, uint32_t vec_id, int wit
                            density_q16, nbits, (u64*)ctx->scratch, nwords64, (u64)nb_from * 1024u);
         KCHK();
     }
-    return vec_from_raw(ctx, shard_bits, nblocks, optimize, out);
+    return vec_from_raw(ctx, win.bits, nblocks, optimize, out);
 ABI_END }
 
 int bmx_vec_generate(bmx_ctx* ctx, uint64_t seed, uint32_t vec_id, int with_common,
@@ -1482,20 +1523,11 @@ static int ids_import_t(bmx_ctx* ctx, const T* d_ids, uint64_t n, uint64_t nbits
         if (max_id >= (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "id beyond the 2^20-block limit"; return BMX_ERR_RANGE; }
         nbits = std::max<uint64_t>(nbits, max_id + 1);                              // sync_size (src/bm.h:2516)
     }
-    const uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nb_to > nblocks64) nb_to = (uint32_t)nblocks64;
-    if (nb_from > nb_to) { g_last_error = "nb_from > nb_to"; return BMX_ERR_RANGE; }
-    const uint32_t nbl = nb_to - nb_from;
-    const uint64_t lo = (uint64_t)nb_from * BMX_BLOCK_BITS, hi = std::min<uint64_t>(nbits, (uint64_t)nb_to * BMX_BLOCK_BITS);
-    Owned<bmx_vec> v = vec_alloc_host(ctx, hi > lo ? hi - lo : 0, nbl);
-    if (!n || !nbl) {
-        if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
-        if (nbl) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nbl * 8, ctx->stream));
-        v->counts[BMX_NULL] = nbl;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        *out = v.release();
-        return BMX_OK;
-    }
+    ShardWindow win;
+    if ((rc = shard_window(nbits, nb_from, nb_to, &win))) return rc;
+    const uint32_t nbl = win.nblocks;
+    if (!n || !nbl) return vec_all_null(ctx, win.bits, nbl, out);
+    Owned<bmx_vec> v = vec_alloc_host(ctx, win.bits, nbl);
     // 2. the touched blocks in block order: tblk[t] = block, ids of entry t = src[tbeg[t] .. tbeg[t + 1])
     u32* d_tot = (u32*)(ctx->d_small + 8);                                          // {sum, touched blocks}
     const uint32_t cap = sorted ? (uint32_t)std::min<uint64_t>(n, (max_id >> 16) + 1) : (uint32_t)std::min<uint64_t>(n, nbl);
@@ -1551,16 +1583,12 @@ static int ids_import_t(bmx_ctx* ctx, const T* d_ids, uint64_t n, uint64_t nbits
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_stats<u16>), wgrid, dim3(256), 0, ctx->stream, (const u16*)src, (const u32*)d_tblk,
                             (const u32*)d_tbeg, (const u32*)d_tot, cap, nb_from, nbl, optimize, (BlockStat*)d_st);
     KCHK();
-    hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, (const BlockStat*)d_st, cap, (u32*)d_offs, ctx->d_small);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const uint32_t n_bit = (uint32_t)ctx->h_small[0]; const uint64_t gap_words = ctx->h_small[1];
-    v->counts[BMX_BIT] = (uint32_t)ctx->h_small[2 + K_BIT]; v->counts[BMX_GAP] = (uint32_t)ctx->h_small[2 + K_GAP];
-    v->counts[BMX_FULL] = (uint32_t)ctx->h_small[2 + K_FULL];
+    Layout lay;
+    if ((rc = layout_read(ctx, (const BlockStat*)d_st, cap, (u32*)d_offs, &lay))) return rc;
+    memcpy(v->counts, lay.counts, sizeof(v->counts));
     v->counts[BMX_NULL] = nbl - v->counts[BMX_BIT] - v->counts[BMX_GAP] - v->counts[BMX_FULL];   // (untouched blocks too)
     // 4. the vector: NULL descriptors, then the touched blocks
-    if ((rc = vec_alloc_device(v.get(), n_bit, gap_words))) return rc;
+    if ((rc = vec_alloc_device(v.get(), lay.n_bit, lay.gap_words))) return rc;
     HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nbl * 8, ctx->stream));
     if (sorted) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ids_emit<T>), wgrid, dim3(256), 0, ctx->stream, (const T*)src, (const u32*)d_tblk,
                                    (const u32*)d_tbeg, (const u32*)d_tot, cap, nb_from, nbl, (const BlockStat*)d_st, (const u32*)d_offs,
@@ -1660,20 +1688,11 @@ static int rng_import_t(bmx_ctx* ctx, const T* d_pairs, uint64_t n, uint64_t nbi
         if (max_end >= (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "range end beyond the 2^20-block limit"; return BMX_ERR_RANGE; }
         nbits = std::max<uint64_t>(nbits, max_end + 1);
     }
-    const uint64_t nblocks64 = (nbits + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nb_to > nblocks64) nb_to = (uint32_t)nblocks64;
-    if (nb_from > nb_to) { g_last_error = "nb_from > nb_to"; return BMX_ERR_RANGE; }
-    const uint32_t nbl = nb_to - nb_from;
-    const uint64_t lo = (uint64_t)nb_from * BMX_BLOCK_BITS, hi = std::min<uint64_t>(nbits, (uint64_t)nb_to * BMX_BLOCK_BITS);
-    Owned<bmx_vec> v = vec_alloc_host(ctx, hi > lo ? hi - lo : 0, nbl);
-    if (!n || !nbl) {
-        if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
-        if (nbl) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nbl * 8, ctx->stream));
-        v->counts[BMX_NULL] = nbl;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        *out = v.release();
-        return BMX_OK;
-    }
+    ShardWindow win;
+    if ((rc = shard_window(nbits, nb_from, nb_to, &win))) return rc;
+    const uint32_t nbl = win.nblocks;
+    if (!n || !nbl) return vec_all_null(ctx, win.bits, nbl, out);
+    Owned<bmx_vec> v = vec_alloc_host(ctx, win.bits, nbl);
     // 2. per block of the shard, in block order: its pairs (sorted and separated) or its bucket of pieces, and its stats
     DevBuf d_st(ctx), d_offs(ctx), d_pfirst(ctx), d_pcnt(ctx), d_cnt(ctx), d_diff(ctx), d_pend(ctx), d_cover(ctx), d_bucket(ctx);
     if ((rc = dmalloc(ctx, &d_st.p, (size_t)nbl * sizeof(BlockStat))) || (rc = dmalloc(ctx, &d_offs.p, (size_t)nbl * 4))) return rc;
@@ -1708,15 +1727,11 @@ static int rng_import_t(bmx_ctx* ctx, const T* d_pairs, uint64_t n, uint64_t nbi
         d_cnt.reset(); d_cover.reset();                           // (pooled: the next user is enqueued behind these kernels)
     }
     // 3. layout
-    hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, (const BlockStat*)d_st, nbl, (u32*)d_offs, ctx->d_small);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const uint32_t n_bit = (uint32_t)ctx->h_small[0]; const uint64_t gap_words = ctx->h_small[1];
-    v->counts[BMX_BIT] = (uint32_t)ctx->h_small[2 + K_BIT]; v->counts[BMX_GAP] = (uint32_t)ctx->h_small[2 + K_GAP];
-    v->counts[BMX_FULL] = (uint32_t)ctx->h_small[2 + K_FULL]; v->counts[BMX_NULL] = (uint32_t)ctx->h_small[2 + K_NULL];
+    Layout lay;
+    if ((rc = layout_read(ctx, (const BlockStat*)d_st, nbl, (u32*)d_offs, &lay))) return rc;
+    memcpy(v->counts, lay.counts, sizeof(v->counts));
     // 4. the vector: every block's wave writes its descriptor
-    if ((rc = vec_alloc_device(v.get(), n_bit, gap_words))) return rc;
+    if ((rc = vec_alloc_device(v.get(), lay.n_bit, lay.gap_words))) return rc;
     if (sorted) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rng_emit_sorted<T>), wgrid, dim3(256), 0, ctx->stream, d_pairs, nb_from, nbl,
                                    (const BlockStat*)d_st, (const u32*)d_offs, (const u32*)d_pfirst, (const u32*)d_pcnt,
                                    v->d_bits, v->d_gaps, v->d_desc);
@@ -1833,11 +1848,11 @@ static int vec_build_ord(bmx_ctx* ctx, bmx_vec* v)
 {
     if (v->d_ord || !v->nblocks) { v->ord_lazy = false; return BMX_OK; }
     int rc;
-    if ((rc = dmalloc(ctx, (void**)&v->d_ord, (size_t)v->nblocks * 4))) return rc;
-    hipLaunchKernelGGL(k_ord_from_desc, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)v->d_desc, v->nblocks, v->d_ord);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { dfree(ctx, v->d_ord); v->d_ord = nullptr; return fail_hip(e, "k_ord_from_desc", __LINE__); }
-    v->ord_lazy = false;
+    DevBuf ord(ctx);
+    if ((rc = dmalloc(ctx, &ord.p, (size_t)v->nblocks * 4))) return rc;
+    hipLaunchKernelGGL(k_ord_from_desc, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)v->d_desc, v->nblocks, (u32*)ord);
+    KCHK();
+    v->d_ord = (u32*)ord.release(); v->ord_lazy = false;
     return BMX_OK;
 }
 
@@ -1879,34 +1894,29 @@ static int vec_indices_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out
     const uint32_t nblocks = v->nblocks;
     if (!nblocks) return BMX_OK;
     if (width == 4 && (uint64_t)nblocks > 65536ull) { g_last_error = "32-bit positions cannot address this vector: use width 8"; return BMX_ERR_RANGE; }
-    DevBuf d_bc(ctx), d_rc(ctx), host_out(ctx);
+    DevBuf d_rc(ctx), d_bc(ctx), host_out(ctx);                    // (given back in reverse: host_out, d_bc, d_rc)
     if ((rc = dmalloc(ctx, &d_bc.p, (size_t)nblocks * 4)) || (rc = dmalloc(ctx, &d_rc.p, (size_t)nblocks * 8))) return rc;
-    hipLaunchKernelGGL(k_block_counts, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)d_bc);
+    const dim3 wgrid((nblocks + 3) / 4);
+    hipLaunchKernelGGL(k_block_counts, wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)d_bc);
     hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, nblocks, (u64*)d_rc, ctx->d_small);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    uint64_t total = e == hipSuccess ? ctx->h_small[0] : 0;
-    if (e == hipSuccess) {
-        *n = total;
-        if (total > cap) { rc = BMX_ERR_RANGE; g_last_error = "output buffer too small for the positions (n holds the number needed)"; }
-        else if (total) {
-            if (out_is_host) rc = dmalloc(ctx, &host_out.p, (size_t)total * (size_t)width);
-            void* d_out = out_is_host ? host_out.p : out;
-            if (!rc) {
-                if (width == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_indices<u64>), dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                                                   (const u64*)v->d_desc, nblocks, (const u64*)d_rc, (u64*)d_out, total, 0ull);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_indices<u32>), dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                                        (const u64*)v->d_desc, nblocks, (const u64*)d_rc, (u32*)d_out, total, 0ull);
-                e = hipGetLastError();
-                if (e == hipSuccess && out_is_host) e = hipMemcpyAsync(out, d_out, (size_t)total * (size_t)width, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            }
-        }
-    }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); rc = fail_hip(e, "bmx_vec_to_indices", __LINE__); }
-    host_out.reset(); d_bc.reset(); d_rc.reset();
-    return rc;
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint64_t total = ctx->h_small[0];
+    *n = total;
+    if (total > cap) { g_last_error = "output buffer too small for the positions (n holds the number needed)"; return BMX_ERR_RANGE; }
+    if (!total) return BMX_OK;
+    const size_t bytes = (size_t)total * (size_t)width;
+    if (out_is_host && (rc = dmalloc(ctx, &host_out.p, bytes))) return rc;
+    void* d_out = out_is_host ? host_out.p : out;
+    if (width == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_indices<u64>), wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks,
+                                       (const u64*)d_rc, (u64*)d_out, total, 0ull);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_expand_indices<u32>), wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks,
+                            (const u64*)d_rc, (u32*)d_out, total, 0ull);
+    KCHK();
+    if (out_is_host) HIPCHK(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BMX_OK;
 }
 
 int bmx_vec_to_indices(bmx_ctx* ctx, const bmx_vec* v, int width, void* out, uint64_t cap, uint64_t* n)
@@ -2649,12 +2659,10 @@ static int result_finish(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, boo
     int rc;
     uint32_t nblocks = v->nblocks;
     if (!nblocks) return BMX_OK;
-    hipLaunchKernelGGL(k_scan_layout, dim3(1), dim3(1024), 0, ctx->stream, st, nblocks, offs, ctx->d_small);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 6 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    uint64_t gap_words = gaps_done ? 0 : ctx->h_small[1];
-    for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
+    Layout lay;
+    if ((rc = layout_read(ctx, st, nblocks, offs, &lay))) return rc;
+    uint64_t gap_words = gaps_done ? 0 : lay.gap_words;
+    memcpy(v->counts, lay.counts, sizeof(v->counts));
     bool pending = false;
     if (gap_words) {
         size_t b_gaps = (size_t)gap_words * 2 + 64;      // + guard, see vec_alloc_device
@@ -2669,13 +2677,12 @@ static int result_finish(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, boo
     uint32_t live = v->counts[BMX_BIT];
     uint4* old_slab = nullptr;
     if (live && (uint64_t)live * 8u < (uint64_t)nblocks * 7u) {
-        uint4* packed = nullptr;
-        if ((rc = dmalloc(ctx, (void**)&packed, (size_t)live * 8192))) return rc;
+        DevBuf packed(ctx);
+        if ((rc = dmalloc(ctx, &packed.p, (size_t)live * 8192))) return rc;
         hipLaunchKernelGGL(k_compact_bits, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                           (const uint4*)v->d_bits, nblocks, (const BlockStat*)st, (const u32*)offs, packed, v->d_desc);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { dfree(ctx, packed); return fail_hip(e, "k_compact_bits", __LINE__); }
-        old_slab = v->d_bits; v->d_bits = packed; v->n_bit = live;
+                           (const uint4*)v->d_bits, nblocks, (const BlockStat*)st, (const u32*)offs, (uint4*)packed, v->d_desc);
+        KCHK();
+        old_slab = v->d_bits; v->d_bits = (uint4*)packed.release(); v->n_bit = live;
         pending = true;
     } else if (live && live < nblocks) {
         if ((rc = dmalloc(ctx, (void**)&v->d_ord, (size_t)nblocks * 4))) return rc;
@@ -2691,6 +2698,15 @@ static int result_finish(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, boo
     if (live == 0) {                          // nothing lives in the slab: give it back
         dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0;
     }
+    return BMX_OK;
+}
+
+// The tail of a call whose kernel folded the kinds of its result into h_small[2..5] (the stream has been synchronised): when
+// every block came out a bit-block there is nothing for the layout scan to lay out, else result_finish
+static int result_finish_folded(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs)
+{
+    if (ctx->h_small[2 + BMX_GAP] != 0 || ctx->h_small[2 + BMX_BIT] != v->nblocks) return result_finish(ctx, v, st, offs);
+    for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
     return BMX_OK;
 }
 
@@ -2752,17 +2768,14 @@ static int gap_slab_trim(bmx_ctx* ctx, bmx_vec* v, uint64_t bound, uint64_t used
     int rc;
     if (!used) { dfree(ctx, v->d_gaps); v->d_gaps = nullptr; v->gap_words = 0; return BMX_OK; }
     if (bound > 2 * used + 4096 && (size_t)(bound - used) * 2 > slack_ok) {
-        u16* small_ = nullptr;
-        if ((rc = dmalloc(ctx, (void**)&small_, (size_t)used * 2 + 64))) return rc;
-        hipError_t e = hipMemcpyAsync(small_, v->d_gaps, (size_t)used * 2, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_rebase_desc, dim3((v->nblocks + 255) / 256), dim3(256), 0, ctx->stream, (const u64*)v->d_desc, v->d_desc, v->nblocks,
-                               (u64)(uintptr_t)v->d_bits, (u64)(uintptr_t)v->d_bits, (u64)(uintptr_t)v->d_gaps, (u64)(uintptr_t)small_);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); dfree(ctx, small_); return fail_hip(e, "gap_slab_trim", __LINE__); }
+        DevBuf small_(ctx);
+        if ((rc = dmalloc(ctx, &small_.p, (size_t)used * 2 + 64))) return rc;
+        HIPCHK(hipMemcpyAsync(small_.p, v->d_gaps, (size_t)used * 2, hipMemcpyDeviceToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_rebase_desc, dim3((v->nblocks + 255) / 256), dim3(256), 0, ctx->stream, (const u64*)v->d_desc, v->d_desc, v->nblocks,
+                           (u64)(uintptr_t)v->d_bits, (u64)(uintptr_t)v->d_bits, (u64)(uintptr_t)v->d_gaps, (u64)(uintptr_t)small_.p);
+        KCHK();
         dfree(ctx, v->d_gaps);
-        v->d_gaps = small_; v->gap_words = used; v->bytes += (size_t)used * 2 + 64;
+        v->d_gaps = (u16*)small_.release(); v->gap_words = used; v->bytes += (size_t)used * 2 + 64;
     } else { v->gap_words = used; v->bytes += (size_t)bound * 2 + 64; }
     return BMX_OK;
 }
@@ -2803,18 +2816,7 @@ int bmx_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int opt_co
     if (a == b) {
         // aliasing as the reference handles it up front: AND / OR of a vector with itself is a block-for-block copy
         // (src/bm.h:6191-6195, 5984-5988), XOR / SUB are empty (:6081, 6412); nothing is re-optimised
-        if (op == BMX_AND || op == BMX_OR) return vec_clone(ctx, a, result);
-        Owned<bmx_vec> v; BlockStat* st; u32* offs;
-        if ((rc = result_begin(ctx, nbits, nblocks, &v, &st, &offs))) return rc;
-        if (nblocks) {
-            hipError_t e = hipMemsetAsync(v->d_desc, 0, (size_t)nblocks * 8, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) return fail_hip(e, "bmx_op2", __LINE__);
-        }
-        v->counts[BMX_NULL] = nblocks;
-        dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0;
-        *result = v.release();
-        return BMX_OK;
+        return op == BMX_AND || op == BMX_OR ? vec_clone(ctx, a, result) : vec_all_null(ctx, nbits, nblocks, result);
     }
     Owned<bmx_vec> v; BlockStat* st; u32* offs;
     if ((rc = result_begin(ctx, nbits, nblocks, &v, &st, &offs))) return rc;
@@ -2870,14 +2872,9 @@ int bmx_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int opt_co
             *result = v.release();
             return BMX_OK;
         }
-        if ((no_gap || folded) && ctx->h_small[2 + BMX_GAP] == 0 && ctx->h_small[2 + BMX_BIT] == nblocks) {
-            for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
-            if (counted) { v->count = ctx->h_small[8]; v->count_valid = true; }
-            *result = v.release();
-            return BMX_OK;
-        }
     }
-    if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;       // (synchronises: the folded count has arrived too)
+    // (result_finish synchronises: the folded count has arrived either way)
+    if ((rc = nblocks && (no_gap || folded) ? result_finish_folded(ctx, v.get(), st, offs) : result_finish(ctx, v.get(), st, offs))) return rc;
     if (counted) { v->count = ctx->h_small[8]; v->count_valid = true; }
     *result = v.release();
     return BMX_OK;
@@ -3130,23 +3127,39 @@ static int use_direct(const bmx_ctx* ctx, uint32_t ncols, size_t n_ops)
     return (ncols <= (uint32_t)ctx->direct_cols && n_ops <= DIRECT_MAX_OPS) ? SPLIT_WAVES : 0;
 }
 
-// operand table on the device: n descriptor-table pointers, then n block counts (u32); one staged copy
-static int direct_table(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb, DevBuf& d_tab)
+// The operand table of a call: n descriptor-table pointers, then n block counts (u32), with what the list looks like.
+// operand_list checks the list (a, then b) and fills the host side; direct_table puts it on the device -- one pooled block, one
+// staged copy, nothing the caller has to wait for -- and sets the two pointers the kernels take.
+struct OperandTable {
+    std::vector<u64> tab; size_t n = 0;
+    uint32_t ncols = 0; uint64_t nbits = 0; bool has_gap = false, has_bit = false;
+    const u64* const* d_descs = nullptr; const u32* d_nblk = nullptr;
+};
+// planes: a null entry is a plane that does not exist (slice_compare_impl): its row stays {null, 0 blocks}
+static int operand_list(const bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b, size_t nb, bool planes, OperandTable* t)
 {
-    size_t n = na + nb;
-    std::vector<u64> tab(n + (n + 1) / 2);
-    u32* nb32 = reinterpret_cast<u32*>(tab.data() + n);
+    const size_t n = t->n = na + nb;
+    t->tab.assign(n + (n + 1) / 2, 0);
+    u32* nb32 = reinterpret_cast<u32*>(t->tab.data() + n);
     for (size_t i = 0; i < n; ++i) {
         const bmx_vec* o = i < na ? a[i] : b[i - na];
-        if (!o || o->ctx != ctx) { g_last_error = "operand is null or belongs to another context"; return BMX_ERR_BADARG; }
-        tab[i] = (u64)(uintptr_t)o->d_desc; nb32[i] = o->nblocks;
+        if (!o && planes) continue;
+        if (!o || o->ctx != ctx) { g_last_error = planes ? "slice belongs to another context" : "operand is null or belongs to another context"; return BMX_ERR_BADARG; }
+        t->tab[i] = (u64)(uintptr_t)o->d_desc; nb32[i] = o->nblocks;
+        t->ncols = std::max(t->ncols, o->nblocks); t->nbits = std::max(t->nbits, o->nbits);
+        t->has_gap |= o->counts[BMX_GAP] != 0; t->has_bit |= o->counts[BMX_BIT] != 0;
     }
+    return BMX_OK;
+}
+static int direct_table(bmx_ctx* ctx, OperandTable* t, DevBuf& d_tab)
+{
     int rc;
-    if ((rc = dmalloc(ctx, &d_tab.p, tab.size() * 8)) || (rc = h2d_staged(ctx, d_tab.p, tab.data(), tab.size() * 8))) d_tab.reset();
-    return rc;
+    if ((rc = dmalloc(ctx, &d_tab.p, t->tab.size() * 8)) || (rc = h2d_staged(ctx, d_tab.p, t->tab.data(), t->tab.size() * 8))) { d_tab.reset(); return rc; }
+    t->d_descs = (const u64* const*)d_tab.p; t->d_nblk = (const u32*)((const u64*)d_tab.p + t->n);
+    return BMX_OK;
 }
 
-static int direct_launch(int mode, bmx_ctx* ctx, const void* d_tab, size_t n_and, size_t n_sub, u32 col_from, u32 col_to, int opt_compress,
+static int direct_launch(int mode, bmx_ctx* ctx, const OperandTable& t, size_t n_and, size_t n_sub, u32 col_from, u32 col_to, int opt_compress,
                          bmx_vec* v, BlockStat* st, int has_mask, u32 mf, u32 mt)
 {
     if (col_to <= col_from) return BMX_OK;
@@ -3158,7 +3171,7 @@ static int direct_launch(int mode, bmx_ctx* ctx, const void* d_tab, size_t n_and
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(fn, dim3(col_to - col_from), dim3(split * 64), lds, ctx->stream,
-                           (const u64* const*)d_tab, (const u32*)((const u64*)d_tab + n), (u32)n_and, (u32)n_sub, col_from, col_to,
+                           t.d_descs, t.d_nblk, (u32)n_and, (u32)n_sub, col_from, col_to,
                            opt_compress, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, has_mask, mf, mt, ctx->d_small);
         e = hipGetLastError();
     }
@@ -3208,24 +3221,17 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
     ARGCHK(ctx && result && (n == 0 || src) && n <= 65535);
     *result = nullptr;
     int rc = set_dev(ctx); if (rc) return rc;
-    uint32_t ncols = 0; uint64_t nbits = 0; bool has_gap = false, has_bit = false;
-    std::vector<const u64*> descs(std::max<size_t>(n, 1), nullptr);
-    std::vector<u32> nblk(std::max<size_t>(n, 1), 0);
-    for (size_t i = 0; i < n; ++i) {
-        if (!src[i] || src[i]->ctx != ctx) { g_last_error = "operand is null or belongs to another context"; return BMX_ERR_BADARG; }
-        descs[i] = src[i]->d_desc; nblk[i] = src[i]->nblocks;
-        ncols = std::max(ncols, src[i]->nblocks); nbits = std::max(nbits, src[i]->nbits);
-        has_gap |= src[i]->counts[BMX_GAP] != 0;
-        has_bit |= src[i]->counts[BMX_BIT] != 0;
-    }
+    OperandTable ops;
+    if ((rc = operand_list(ctx, src, n, nullptr, 0, false, &ops))) return rc;
+    const uint32_t ncols = ops.ncols; const bool has_gap = ops.has_gap, has_bit = ops.has_bit;
     Owned<bmx_vec> v; BlockStat* st; u32* offs;
     bmx_coll* packed = nullptr; std::vector<u32> members; bool packed_full = false;
     CollPin pin;
-    if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;      // empty list => cleared target (:1105)
+    if ((rc = result_begin(ctx, ops.nbits, ncols, &v, &st, &offs))) return rc;  // empty list => cleared target (:1105)
     if (use_direct(ctx, ncols, n)) {
         DevBuf d_tab(ctx);
-        if ((rc = direct_table(ctx, src, n, nullptr, 0, d_tab))) return rc;
-        rc = direct_launch(DIRECT_OR, ctx, d_tab.p, n, 0, 0u, ncols, opt_compress, v.get(), st, 0, 0u, 0u);
+        if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
+        rc = direct_launch(DIRECT_OR, ctx, ops, n, 0, 0u, ncols, opt_compress, v.get(), st, 0, 0u, 0u);
         if (!rc) rc = result_finish(ctx, v.get(), st, offs);
         else (void)hipStreamSynchronize(ctx->stream);
         d_tab.reset();
@@ -3254,17 +3260,11 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
         const bool fold = !opt_compress && ctx->coll_window == 0;
         rc = coll_launch(COLL_OR, ctx, packed, nullptr, 0u, ncols, opt_compress, nullptr, v.get(), st, 0u, 0xFFFFFFFFu,
                          fold ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr});
-        bool done = false;
         if (!rc && fold) {
             hipError_t e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = fail_hip(e, "k_coll_apply", __LINE__);
-            else if (ctx->h_small[2 + BMX_GAP] == 0 && ctx->h_small[2 + BMX_BIT] == ncols) {
-                for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
-                done = true;
-            }
-        }
-        if (!rc && !done) rc = result_finish(ctx, v.get(), st, offs);
-        else if (rc) (void)hipStreamSynchronize(ctx->stream);
+            rc = e == hipSuccess ? result_finish_folded(ctx, v.get(), st, offs) : fail_hip(e, "k_coll_apply", __LINE__);
+        } else if (!rc) rc = result_finish(ctx, v.get(), st, offs);
+        else (void)hipStreamSynchronize(ctx->stream);
         if (rc) return rc;
     } else if (rc) { return rc;
     } else if (n >= 64 && ncols && has_gap && !has_bit && or_rows_wanted(ctx, src, n)) {
@@ -3298,16 +3298,12 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
         d_tab.reset();
         if (e != hipSuccess) return fail_hip(e, "bmx_agg_or (rows)", __LINE__);
         const uint64_t total = ctx->h_small[8];
-        if (ctx->h_small[2 + BMX_GAP] == 0 && ctx->h_small[2 + BMX_BIT] == ncols) {
-            for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
-        } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+        if ((rc = result_finish_folded(ctx, v.get(), st, offs))) return rc;
         v->count = total; v->count_valid = true;
     } else if (n >= 64 && ncols && has_gap && !has_bit) {
         // many GAP-only operands: column-tile kernel straight from the descriptor tables (no sort pass)
-        DevBuf d_descs(ctx), d_nblk(ctx);
-        if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4))) return rc;
-        hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+        DevBuf d_tab(ctx);
+        if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
         size_t lds = (size_t)OR_TILE * 8192 + OR_TILE * 4;
         // or_tile: 0 = single-bit fast path (default), 1 = the round-1 run code, 2 = two operands per lane per step;
         // tuning build, or_window = -9: loads only (the memory floor of the access pattern)
@@ -3318,44 +3314,27 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
 #else
         auto tiled = ctx->or_tile == 0 ? k_agg_or_gap_tiled<1, 1> : ctx->or_tile == 2 ? k_agg_or_gap_tiled<1, 2> : k_agg_or_gap_tiled<0, 1>;
 #endif
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(tiled), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            u32 win = ctx->or_window <= 0 ? ntiles : (u32)ctx->or_window;        // windows measured: no gain here
-            u32 nwin = (ntiles + win - 1) / win, per = (ntiles + nwin - 1) / nwin;
-            for (u32 t0 = 0; t0 < ntiles && e == hipSuccess; t0 += per) {
-                hipLaunchKernelGGL(tiled, dim3(std::min(per, ntiles - t0)), dim3(1024), lds, ctx->stream,
-                                   (const u64* const*)d_descs, (const u32*)d_nblk, (u32)n, ncols, opt_compress, v->d_bits, v->d_desc, st, t0);
-                e = hipGetLastError();
-            }
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tiled), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        u32 win = ctx->or_window <= 0 ? ntiles : (u32)ctx->or_window;        // windows measured: no gain here
+        u32 nwin = (ntiles + win - 1) / win, per = (ntiles + nwin - 1) / nwin;
+        for (u32 t0 = 0; t0 < ntiles; t0 += per) {
+            hipLaunchKernelGGL(tiled, dim3(std::min(per, ntiles - t0)), dim3(1024), lds, ctx->stream,
+                               ops.d_descs, ops.d_nblk, (u32)n, ncols, opt_compress, v->d_bits, v->d_desc, st, t0);
+            KCHK();
         }
-        if (e == hipSuccess) rc = result_finish(ctx, v.get(), st, offs);
-        else rc = fail_hip(e, "bmx_agg_or (tiled)", __LINE__);
-        (void)hipStreamSynchronize(ctx->stream);
-        d_descs.reset(); d_nblk.reset();
-        if (rc) return rc;
+        if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     } else if (n && ncols) {
-        DevBuf d_descs(ctx), d_nblk(ctx), d_dmat(ctx);
-        size_t b_dmat = (size_t)ncols * (n + 2) * 8;
-        if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4)) || (rc = dmalloc(ctx, &d_dmat.p, b_dmat))) return rc;
-        hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_or_sort, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream,
-                               (const u64* const*)d_descs, (const u32*)d_nblk, (u32)n, ncols, (u64*)d_dmat);
-            size_t lds = has_gap ? 4 * 2048 * 4 : 0;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_agg_or<2>), dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
-                               (const u64*)d_dmat, (u32)n, ncols, opt_compress, ctx->xcd_swz,
-                               v->d_bits, v->d_desc, st);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) rc = result_finish(ctx, v.get(), st, offs);
-        else rc = fail_hip(e, "bmx_agg_or", __LINE__);
-        (void)hipStreamSynchronize(ctx->stream);
-        d_descs.reset(); d_nblk.reset(); d_dmat.reset();
-        if (rc) return rc;
-    } else if (ncols) {
-        HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)ncols * 8, ctx->stream));
-        v->counts[BMX_NULL] = ncols;
+        DevBuf d_dmat(ctx), d_tab(ctx);                                   // (given back in reverse: the table, then the rows)
+        if ((rc = direct_table(ctx, &ops, d_tab)) || (rc = dmalloc(ctx, &d_dmat.p, (size_t)ncols * (n + 2) * 8))) return rc;
+        hipLaunchKernelGGL(k_or_sort, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, ops.d_descs, ops.d_nblk, (u32)n, ncols, (u64*)d_dmat);
+        size_t lds = has_gap ? 4 * 2048 * 4 : 0;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_agg_or<2>), dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
+                           (const u64*)d_dmat, (u32)n, ncols, opt_compress, ctx->xcd_swz,
+                           v->d_bits, v->d_desc, st);
+        KCHK();
+        if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     *result = v.release();
     return BMX_OK;
@@ -3434,26 +3413,19 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
     uint64_t nbits = 0; uint32_t ncols = 0;
     for (size_t i = 0; i < n_and; ++i) { ARGCHK(src_and[i]); nbits = std::max(nbits, src_and[i]->nbits); ncols = std::max(ncols, src_and[i]->nblocks); }
     for (size_t i = 0; i < n_sub; ++i) { ARGCHK(src_sub[i]); nbits = std::max(nbits, src_sub[i]->nbits); ncols = std::max(ncols, src_sub[i]->nblocks); }
+    if (!n_and) return vec_all_null(ctx, nbits, ncols, result);     // empty AND group => cleared target (:1170-1174)
     Owned<bmx_vec> v; BlockStat* st; u32* offs;
-    if (!n_and) {                                               // empty AND group => cleared target (:1170-1174)
-        if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-        if (ncols) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)ncols * 8, ctx->stream));
-        v->counts[BMX_NULL] = ncols;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        *result = v.release();
-        return BMX_OK;
-    }
     // small collection (few columns, many operands): one launch straight from the descriptor tables (k_direct)
     if (use_direct(ctx, ncols, n_and + n_sub)) {
-        DevBuf d_tab(ctx);
-        if ((rc = direct_table(ctx, src_and, n_and, src_sub, n_sub, d_tab))) return rc;
+        OperandTable ops; DevBuf d_tab(ctx);
+        if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = direct_table(ctx, &ops, d_tab))) return rc;
         if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-        rc = direct_launch(DIRECT_AND_SUB, ctx, d_tab.p, n_and, n_sub, 0u, ncols, 1, v.get(), st, 0, 0u, 0u);
+        rc = direct_launch(DIRECT_AND_SUB, ctx, ops, n_and, n_sub, 0u, ncols, 1, v.get(), st, 0, 0u, 0u);
         if (!rc) rc = result_finish(ctx, v.get(), st, offs);              // synchronises
         else (void)hipStreamSynchronize(ctx->stream);
         d_tab.reset();
         if (rc) return rc;
-        if (any) *any = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
+        if (any) *any = vec_any_block(v.get());
         *result = v.release();
         return BMX_OK;
     }
@@ -3486,7 +3458,7 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
             else (void)hipStreamSynchronize(ctx->stream);
             d_buf.reset();
             if (rc) return rc;
-            if (any) *any = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
+            if (any) *any = vec_any_block(v.get());
             *result = v.release();
             return BMX_OK;
         }
@@ -3511,7 +3483,7 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
     if (!rc) rc = result_finish(ctx, v.get(), st, offs);
     p.reset();
     if (rc) return rc;
-    if (any) *any = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
+    if (any) *any = vec_any_block(v.get());
     *result = v.release();
     return BMX_OK;
 ABI_END }
@@ -3559,7 +3531,7 @@ static int run_results_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
         else rc = agg_and_sub_launch(ctx, p, g, v.get(), st, nb_from, nb_to);
         if (rc) return rc;
         if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
-        if (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP] == 0) continue;   // nothing found: stays NULL (:1406)
+        if (!vec_any_block(v.get())) continue;   // nothing found: stays NULL (:1406)
         res[g] = std::move(v);
         if (counts_out && (rc = bmx_count(ctx, res[g].get(), &counts_out[g]))) return rc;
     }
@@ -3621,7 +3593,7 @@ int bmx_pipeline_run_results_hint(bmx_ctx* ctx, bmx_pipeline* p, uint64_t from, 
         rc = bmx_op2(ctx, BMX_AND, res[g].get(), mask.get(), 1, &m);
         res[g].reset(m);
         if (rc) break;
-        if (m->counts[BMX_FULL] + m->counts[BMX_BIT] + m->counts[BMX_GAP] == 0) { res[g].reset(); continue; }
+        if (!vec_any_block(m)) { res[g].reset(); continue; }
         if (counts_out) rc = bmx_count(ctx, m, &counts_out[g]);
     }
     mask.reset();
@@ -3678,11 +3650,11 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     if (direct) {
         // many operands: a workgroup of 8 waves per column straight from the descriptor tables (k_direct); 64 columns first
         // (a hit in the first blocks is answered after ~1/8 of what two workgroups per CU would read)
-        DevBuf d_tab(ctx);
-        if ((rc = direct_table(ctx, src_and, n_and, src_sub, n_sub, d_tab))) return rc;
+        OperandTable ops; DevBuf d_tab(ctx);
+        if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = direct_table(ctx, &ops, d_tab))) return rc;
         hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
         if (e == hipSuccess)
-            rc = windows(n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) { return direct_launch(DIRECT_FIND_FIRST, ctx, d_tab.p, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt); });
+            rc = windows(n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) { return direct_launch(DIRECT_FIND_FIRST, ctx, ops, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt); });
         if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
         hipError_t e2 = hipStreamSynchronize(ctx->stream);
         d_tab.reset();
@@ -3748,54 +3720,31 @@ static int shift_right_and_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t 
     if (found) *found = 0;
     if (count) *count = 0;
     int rc = set_dev(ctx); if (rc) return rc;
-    uint32_t ncols = 0; uint64_t nbits = 0;
-    std::vector<const u64*> descs(std::max<size_t>(n, 1), nullptr);
-    std::vector<u32> nblk(std::max<size_t>(n, 1), 0);
-    for (size_t i = 0; i < n; ++i) {
-        if (!src[i] || src[i]->ctx != ctx) { g_last_error = "operand is null or belongs to another context"; return BMX_ERR_BADARG; }
-        descs[i] = src[i]->d_desc; nblk[i] = src[i]->nblocks;
-        ncols = std::max(ncols, src[i]->nblocks); nbits = std::max(nbits, src[i]->nbits);
-    }
+    OperandTable ops;
+    if ((rc = operand_list(ctx, src, n, nullptr, 0, false, &ops))) return rc;
+    const uint32_t ncols = ops.ncols;
+    if (!n || !ncols) return result ? vec_all_null(ctx, ops.nbits, ncols, result) : BMX_OK;   // empty list => cleared target (:2499)
     Owned<bmx_vec> v; BlockStat* st = nullptr; u32* offs = nullptr;
-    if (result && (rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;   // empty list => cleared target (:2499)
-    if (!n || !ncols) {
-        if (v && ncols) {
-            hipError_t e = hipMemsetAsync(v->d_desc, 0, (size_t)ncols * 8, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) return fail_hip(e, "bmx_agg_shift_right_and", __LINE__);
-            v->counts[BMX_NULL] = ncols;
-        }
-        if (result) *result = v.release();
-        return BMX_OK;
-    }
-    DevBuf d_descs(ctx), d_nblk(ctx);
-    if ((rc = dmalloc(ctx, &d_descs.p, n * 8)) || (rc = dmalloc(ctx, &d_nblk.p, n * 4))) return rc;
-    hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (result && (rc = result_begin(ctx, ops.nbits, ncols, &v, &st, &offs))) return rc;
+    DevBuf d_tab(ctx);
+    if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
     size_t lds = 4 * 4096 * 4;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_shift_right_and, dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
-                           (const u64* const*)d_descs, (const u32*)d_nblk, (u32)n, ncols, opt_compress, result ? 0 : 1,
-                           ctx->xcd_swz, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && result && any) {
+    hipLaunchKernelGGL(k_shift_right_and, dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
+                       ops.d_descs, ops.d_nblk, (u32)n, ncols, opt_compress, result ? 0 : 1,
+                       ctx->xcd_swz, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots);
+    KCHK();
+    if (result && any) {
         hipLaunchKernelGGL(k_keep_first_block, dim3(1), dim3(1024), 0, ctx->stream, st, v->d_desc, ncols);
-        e = hipGetLastError();
+        KCHK();
     }
-    if (e == hipSuccess && !result) {
+    if (!result) {
         hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess && result) rc = result_finish(ctx, v.get(), st, offs);
-    else if (e != hipSuccess) rc = fail_hip(e, "bmx_agg_shift_right_and", __LINE__);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (!rc && e2 != hipSuccess) rc = fail_hip(e2, "bmx_agg_shift_right_and", __LINE__);
-    d_descs.reset(); d_nblk.reset();
-    if (rc) return rc;
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     if (result) {
-        if (found) *found = (v->counts[BMX_FULL] + v->counts[BMX_BIT] + v->counts[BMX_GAP]) != 0;
+        if (found) *found = vec_any_block(v.get());
         *result = v.release();
     } else {
         *count = ctx->h_small[0];
@@ -3832,58 +3781,45 @@ static int slice_compare_impl(bmx_ctx* ctx, const bmx_vec* const* slices, size_t
     uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
     if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
     uint32_t ncols = (uint32_t)nblocks64;
-    std::vector<const u64*> descs(std::max<size_t>(nslices, 1), nullptr);
-    std::vector<u32> nblk(std::max<size_t>(nslices, 1), 0);
-    for (size_t i = 0; i < nslices; ++i) {
-        if (!slices[i]) continue;                                           // plane does not exist
-        if (slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-        descs[i] = slices[i]->d_desc; nblk[i] = slices[i]->nblocks;
-    }
+    OperandTable ops;
+    if ((rc = operand_list(ctx, slices, nslices, nullptr, 0, true, &ops))) return rc;
     const bool sgn = sign_mode != SIGN_NONE || pred == CMP_SRANGE;
     const bool two = pred == BMX_CMP_RANGE || pred == CMP_SRANGE;
     Owned<bmx_vec> v; BlockStat* st = nullptr; u32* offs = nullptr;
     if (result && (rc = result_begin(ctx, size, ncols, &v, &st, &offs))) return rc;
     if (!ncols) { if (result) *result = v.release(); return BMX_OK; }
-    DevBuf d_descs(ctx), d_nblk(ctx);
-    size_t nal = std::max<size_t>(nslices, 1);
-    if ((rc = dmalloc(ctx, &d_descs.p, nal * 8)) || (rc = dmalloc(ctx, &d_nblk.p, nal * 4))) return rc;
-    hipError_t e = hipMemcpyAsync(d_descs.p, descs.data(), nal * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_nblk.p, nblk.data(), nal * 4, hipMemcpyHostToDevice, ctx->stream);
+    DevBuf d_tab(ctx);
+    if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
     u64* d_stat = plane_bytes ? ctx->d_small + 8 : nullptr;
-    if (e == hipSuccess && d_stat) e = hipMemsetAsync(d_stat, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
+    if (d_stat) HIPCHK(hipMemsetAsync(d_stat, 0, 8, ctx->stream));
 #define CMP_ARGS dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, \
-            (const u64* const*)d_descs, (const u32*)d_nblk, (u32)nslices, ncols, pred, v0, v1, size, \
-            not_null ? (const u64*)not_null->d_desc : nullptr, not_null ? not_null->nblocks : 0u, null_correct, \
-            result ? 0 : 1, ctx->xcd_swz, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots, \
-            sign ? (const u64*)sign->d_desc : nullptr, sign ? sign->nblocks : 0u, sign_mode, d_stat
-        if (ctx->range_halves) {                                            // partial-block passes (fewer accumulators, more waves)
-            // (measured: one bound -- half blocks 0.372 ms, quarter blocks 0.422; two bounds -- half blocks 0.536 ms, quarter blocks 0.473)
-            if (sgn) { if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<true, 2, true>), CMP_ARGS);
-                       else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<false, 4, true>), CMP_ARGS); }
-            else if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<true, 2>), CMP_ARGS);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<false, 4>), CMP_ARGS);
-        } else {
-            if (sgn) { if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<true, true>), CMP_ARGS);
-                       else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<false, true>), CMP_ARGS); }
-            else if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<true>), CMP_ARGS);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<false>), CMP_ARGS);
-        }
+        ops.d_descs, ops.d_nblk, (u32)nslices, ncols, pred, v0, v1, size, \
+        not_null ? (const u64*)not_null->d_desc : nullptr, not_null ? not_null->nblocks : 0u, null_correct, \
+        result ? 0 : 1, ctx->xcd_swz, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots, \
+        sign ? (const u64*)sign->d_desc : nullptr, sign ? sign->nblocks : 0u, sign_mode, d_stat
+    if (ctx->range_halves) {                                            // partial-block passes (fewer accumulators, more waves)
+        // (measured: one bound -- half blocks 0.372 ms, quarter blocks 0.422; two bounds -- half blocks 0.536 ms, quarter blocks 0.473)
+        if (sgn) { if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<true, 2, true>), CMP_ARGS);
+                   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<false, 4, true>), CMP_ARGS); }
+        else if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<true, 2>), CMP_ARGS);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<false, 4>), CMP_ARGS);
+    } else {
+        if (sgn) { if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<true, true>), CMP_ARGS);
+                   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<false, true>), CMP_ARGS); }
+        else if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<true>), CMP_ARGS);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<false>), CMP_ARGS);
+    }
 #undef CMP_ARGS
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && !result) {
+    KCHK();
+    if (!result) {
         hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (e == hipSuccess && d_stat) e = hipMemcpyAsync(ctx->h_small + 8, d_stat, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && result) rc = result_finish(ctx, v.get(), st, offs);
-    else if (e != hipSuccess) rc = fail_hip(e, "bmx_slice_compare", __LINE__);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (!rc && e2 != hipSuccess) rc = fail_hip(e2, "bmx_slice_compare", __LINE__);
-    d_descs.reset(); d_nblk.reset();
-    if (rc) return rc;
+    if (d_stat) HIPCHK(hipMemcpyAsync(ctx->h_small + 8, d_stat, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (result && (rc = result_finish(ctx, v.get(), st, offs))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    d_tab.reset();                                          // (before the count pass below allocates)
     if (plane_bytes) *plane_bytes = ctx->h_small[8];
     if (result) {
         *result = v.release();
@@ -4399,18 +4335,6 @@ ABI_END }
 // ---------------------------------------------------------------------------
 // bm::rank_compressor (src/bmalgo.h:452-707; bmx_kernels15.h): n sources against one index, dir 0 = compress, 1 = decompress
 // ---------------------------------------------------------------------------
-static int rankc_empty(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, bmx_vec** out)
-{
-    int rc;
-    Owned<bmx_vec> v = vec_alloc_host(ctx, nbits, nblocks);
-    if ((rc = vec_alloc_device(v.get(), 0, 0))) return rc;
-    if (nblocks) HIPCHK(hipMemsetAsync(v->d_desc, 0, (size_t)nblocks * 8, ctx->stream));
-    v->counts[BMX_NULL] = nblocks;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    *out = v.release();
-    return BMX_OK;
-}
-
 static int rankc_run(bmx_ctx* ctx, int dir, const bmx_vec* idx, const bmx_rs* rs, const bmx_vec* const* srcs, size_t n, int optimize,
                      bmx_vec** outs)
 {
@@ -4449,7 +4373,7 @@ static int rankc_run(bmx_ctx* ctx, int dir, const bmx_vec* idx, const bmx_rs* rs
     for (size_t i = 0; i < n; ++i) {
         if (!srcs[i]) continue;
         if (srcs[i] == idx) { bmx_vec* c = nullptr; if ((rc = vec_clone(ctx, idx, &c))) return rc; res[i].reset(c); continue; }
-        if (!total || !nbt) { bmx_vec* c = nullptr; if ((rc = rankc_empty(ctx, nbits_out, nbt, &c))) return rc; res[i].reset(c); continue; }
+        if (!total || !nbt) { bmx_vec* c = nullptr; if ((rc = vec_all_null(ctx, nbits_out, nbt, &c))) return rc; res[i].reset(c); continue; }
         hs[i] = RankcSrc{srcs[i]->d_desc, srcs[i]->nblocks, 0u};
         ++live;
     }
@@ -4483,8 +4407,9 @@ static int rankc_run(bmx_ctx* ctx, int dir, const bmx_vec* idx, const bmx_rs* rs
             for (size_t i = 0; i < n; ++i) {
                 if (!hs[i].desc) continue;
                 Owned<bmx_vec> v = vec_alloc_host(ctx, nbits_out, nbt);
-                for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)tot[i * 8 + 2 + k];
-                if ((rc = vec_alloc_device(v.get(), (uint32_t)tot[i * 8], tot[i * 8 + 1]))) return rc;
+                const Layout lay(&tot[i * 8]);
+                memcpy(v->counts, lay.counts, sizeof(v->counts));
+                if ((rc = vec_alloc_device(v.get(), lay.n_bit, lay.gap_words))) return rc;
                 ho[i] = RankcOut{v->d_bits, v->d_gaps, v->d_desc, 0ull};
                 res[i] = std::move(v);
             }
