@@ -767,6 +767,13 @@ static u32 pipe_window_cap(u32 wg)
     u32 per_cu = wpb >= 7u ? 1u : 12u / wpb;                          // 147 VGPRs: 12 waves per CU
     return 256u * per_cu * wpb;
 }
+// n columns (or tiles) in launches of at most cap each (0 = one launch), cut evenly: no short last window
+struct Windows { u32 nwin, per; };
+static Windows even_windows(u32 n, u32 cap)
+{
+    const u32 nwin = (cap && n) ? (n + cap - 1u) / cap : 1u;
+    return {nwin, (n + nwin - 1u) / nwin};
+}
 static void pipe_plan(const bmx_ctx* ctx, u64 nitems, u32 ngroups, u32& rows, u32& wg, u32& unroll, u32& window)
 {
     rows = (u32)ctx->pipe_rows;
@@ -2207,6 +2214,14 @@ static bmx_coll* coll_by_id(bmx_ctx* ctx, uint64_t id)
     for (bmx_coll* c : ctx->colls) if (c->id == id) return c;
     return nullptr;
 }
+// do the collections the pipeline names still serve it?  Both ids resolve and the member table is on the device
+static bool pipe_colls_valid(bmx_ctx* ctx, const bmx_pipeline* p, bmx_coll** a, bmx_coll** s)
+{
+    *a = coll_by_id(ctx, p->cm_a_id); *s = coll_by_id(ctx, p->cm_s_id);
+    const bool ok = *a && (!p->cm_s_id || *s) && p->cm_buf;
+    if (!ok) *a = *s = nullptr;
+    return ok;
+}
 static int pipe_resolve_colls(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, bmx_coll** a, bmx_coll** s)
 {
     *a = nullptr; *s = nullptr;
@@ -2260,183 +2275,178 @@ static int pipe_resolve_colls(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, bmx
             if ((rc = dmalloc(ctx, &buf.p, h.size())) || (rc = h2d_staged(ctx, buf.p, h.data(), h.size()))) return rc;
             p->cm_buf = buf.release(); p->cm_groups_off = goff;
             p->cm_a_id = ca->id; p->cm_s_id = cs ? cs->id : 0;
-            p->cm_full = p->ngroups == 1 && fa && (!tot_sub || fs);
+            p->cm_full = whole;
         }
     }
-    *a = coll_by_id(ctx, p->cm_a_id);
-    *s = coll_by_id(ctx, p->cm_s_id);
-    if (!*a || (p->cm_s_id && !*s) || !p->cm_buf) { *a = nullptr; *s = nullptr; return BMX_OK; }
-    (*a)->last_use = ++ctx->coll_tick; if (*s) (*s)->last_use = ctx->coll_tick;
+    if (pipe_colls_valid(ctx, p, a, s)) { (*a)->last_use = ++ctx->coll_tick; if (*s) (*s)->last_use = ctx->coll_tick; }
     return BMX_OK;
 }
 
 // a subset of a pipeline's arg-groups for one counts launch: the compacted per-group tables k_limit_step wrote
 struct GroupView { const u32* row_off; const u32* and_n; const u32* sub_n; u32 ngroups; const u32* gmask; const u32* gskip; const CollGroup* cgroups; };
-static int pipeline_run_counts_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts, bool may_build, const GroupView* gv = nullptr);
-static int limit_counts_run_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts);
 
-extern "C" {
+// ---- the launch plan of a counts-only run: which kernel serves it, in how many launches, in what shape.  Decided in counts_plan
+// and nowhere else: pipeline_run_counts_impl launches what the plan says, bmx_pipeline_describe prints it.
+enum CountsKernel { CK_COLL_APPLY, CK_COLL_MEMBERS, CK_STAGED, CK_SPLIT, CK_BITS, CK_AND_ROWS, CK_GAPCOUNT, CK_GENERAL };
+enum CollServe { COLLS_NONE, COLLS_WHOLE /* cm_full: one group naming whole collections */, COLLS_MEMBERS };
+static CollServe coll_serve(const bmx_pipeline* p, const bmx_coll* ca) { return !ca ? COLLS_NONE : p->cm_full ? COLLS_WHOLE : COLLS_MEMBERS; }
+struct CountsPlan {
+    CountsKernel kernel;
+    u32 ncols, ngroups; unsigned long long nitems;   // block columns x arg-groups the run covers = (column, group) items
+    Windows win;                            // launches; block columns per launch (at most)
+    u32 rows, wg, unroll, parts; bool nt;   // CK_BITS: pipe_plan's shape, parts = slices per block; CK_GENERAL: unroll alone
+    u32 slots, ar_wg, ar_depth, ar_ipw;     // CK_STAGED: plane blocks staged at a time; CK_AND_ROWS: its shape
+    size_t lds;                             // dynamic LDS bytes per workgroup
+};
+// ngroups: the arg-groups the run covers (all, or those still below their search limit): the items and windows are theirs, the
+// kernel is chosen as for the whole pipeline (p->ngroups, p->n_ops).  No HIP call, no side effect.
+static CountsPlan counts_plan(const bmx_ctx* ctx, const bmx_pipeline* p, u32 nb_from, u32 nb_to, u32 ngroups, CollServe colls)
+{
+    CountsPlan pl{};
+    pl.ncols = nb_to - nb_from; pl.ngroups = ngroups; pl.nitems = (u64)pl.ncols * ngroups; pl.win = {1u, pl.ncols};
+    // many groups over few distinct vectors: every plane block is re-used >= 8 times per column
+    const bool reuse = p->ngroups >= 32 && (uint64_t)p->n_ops >= 8ull * p->nplanes;
+    if (colls != COLLS_NONE) {
+        // GAP-only operands held by packed collections: the column regions of the collections instead of the operands' slabs
+        pl.kernel = colls == COLLS_WHOLE ? CK_COLL_APPLY : CK_COLL_MEMBERS;
+    } else if (p->staged_ok && (ctx->pipe_staged == 1 || (ctx->pipe_staged < 0 && reuse))) {
+        pl.kernel = CK_STAGED; pl.slots = ctx->pipe_slots == 8 ? 8u : 16u; pl.lds = (size_t)pl.slots * 8192;
+    } else if (use_split(ctx, p, pl.nitems)) {
+        // few (column, group) items with long operand lists: 8 waves share an item (k_pipe_split, counts mode)
+        pl.kernel = CK_SPLIT; pl.lds = (size_t)SPLIT_WAVES * 8192;
+    } else if (!p->has_gap) {
+        // bit-block-only fast path: (column, group, slice) items, issued as a sequence of launches over column WINDOWS of at most one
+        // machine-load of waves each (pipe_plan).  Inside a window every wave is in flight at once and the whole chip walks the operand
+        // list in step: at any moment HBM serves ONE contiguous stretch of one operand slab (open-page locality) instead of 256 unrelated
+        // streams, which is what a single launch over all columns degenerates into after its first round of workgroups (measured: +5 % on
+        // the headline, tools/chunk_probe.py; a 1,908-column shard = one window runs at a higher rate than the full-size steady state).
+        u32 window; pipe_plan(ctx, pl.nitems, ngroups, pl.rows, pl.wg, pl.unroll, window);
+        pl.kernel = CK_BITS; pl.parts = 8u / pl.rows; pl.nt = ctx->pipe_nt != 0; pl.lds = (size_t)ctx->pipe_lds;
+        pl.win = even_windows(pl.ncols, window);
+    } else if (use_and_rows(ctx, p)) {
+        // every operand block is GAP (or NULL / FULL): the union of the operands' 0-runs read straight from their slabs
+        // (and_rows_ipw: several consecutive items -- arg-groups of one column -- per workgroup.  Measured on 16 groups x 2 .. 64 operands
+        // over 1e9-bit vectors: 1, 4 and 8 items per workgroup run within 2 % of each other -- such a run is bound by the chain of
+        // dependent round trips inside an item (row header, entries, pieces, fold), not by the dispatch rate -- so the default is 1)
+        pl.kernel = CK_AND_ROWS; pl.ar_wg = (u32)ctx->and_rows_wg; pl.ar_depth = (u32)ctx->and_rows_depth; pl.ar_ipw = ctx->and_rows_ipw > 0 ? (u32)ctx->and_rows_ipw : 1u;
+    } else if (use_gapcount(ctx, p)) {
+        // every operand block is GAP (or NULL / FULL): the counting formulation, one 1024-thread workgroup per (column, group)
+        pl.kernel = CK_GAPCOUNT; pl.lds = (size_t)(16384 * 2 + 2048) * 4;
+    } else {
+        // general kernel (GAP operands present): ONE launch unless pipe_window asks for windows.  Measured (256-way AND, mixed
+        // 1 % and all-GAP 0.3 %): 2,048-column windows cost 19-38 %, 3,072 are neutral -- columns with GAP operands take
+        // unequal time, so a window boundary idles most of the chip while the slowest columns finish.
+        pl.kernel = CK_GENERAL; pl.unroll = ctx->pipe_unroll == 1 ? 1u : ctx->pipe_unroll == 2 ? 2u : 4u; pl.lds = 4 * 2048 * 4;
+        pl.win = even_windows(pl.ncols, ctx->pipe_window > 0 ? (u32)ctx->pipe_window : 0u);
+    }
+    return pl;
+}
 
-int bmx_pipeline_run_counts_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts)
-{ ABI_TRY
-    ARGCHK(ctx && p && p->ctx == ctx && d_counts);
-    if (p->search_limit != ~0ull) return limit_counts_run_dev(ctx, p, nb_from, nb_to, d_counts);
-    return pipeline_run_counts_impl(ctx, p, nb_from, nb_to, d_counts, false);
-ABI_END }
-
-static int pipeline_run_counts_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts, bool may_build, const GroupView* gv)
+static int pipeline_run_counts_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts, bool may_build, const GroupView* gv = nullptr)
 {
     ARGCHK(ctx && p && p->ctx == ctx && d_counts);
     int rc = set_dev(ctx); if (rc) return rc;
     if ((rc = pipe_range(p, nb_from, nb_to))) return rc;
-    // gv: the run covers gv->ngroups arg-groups of the pipeline (those still below their search limit); counts[k] belongs to the
-    // k-th of them.  The kernel is chosen as for the whole pipeline.
+    // gv: the run covers gv->ngroups arg-groups of the pipeline (those still below their search limit); counts[k] is the k-th one's
     const u32 ngroups = gv ? gv->ngroups : p->ngroups;
     HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)std::max(ngroups, 1u) * 8, ctx->stream));
-    u64 nitems64 = (u64)(nb_to - nb_from) * ngroups;
-    if (!nitems64) return BMX_OK;
+    if (nb_from == nb_to || !ngroups) return BMX_OK;
+    bmx_coll *ca = nullptr, *cs = nullptr;
+    if (!p->h_uids.empty() && (rc = pipe_resolve_colls(ctx, p, may_build, &ca, &cs))) return rc;
+    const CountsPlan pl = counts_plan(ctx, p, nb_from, nb_to, ngroups, coll_serve(p, ca));
     const u32* row_off = gv ? gv->row_off : p->d_meta; const u32* and_n = gv ? gv->and_n : p->d_meta + p->ngroups; const u32* sub_n = gv ? gv->sub_n : p->d_meta + 2 * p->ngroups;
-    if (!p->h_uids.empty()) {
-        // GAP-only operands held by packed collections: the column regions of the collections instead of the operands' slabs
-        bmx_coll *ca = nullptr, *cs = nullptr;
-        if ((rc = pipe_resolve_colls(ctx, p, may_build, &ca, &cs))) return rc;
-        if (ca && p->cm_full) return coll_launch(COLL_AND_COUNT, ctx, ca, cs, nb_from, nb_to, 1, (u64*)d_counts, nullptr, nullptr, 0u, 0xFFFFFFFFu);
-        if (ca) return coll_members_launch(CM_AND_COUNT, ctx, ca, cs, (const u32*)p->cm_buf, gv ? gv->cgroups : (const CollGroup*)((const char*)p->cm_buf + p->cm_groups_off),
-                                           ngroups, nb_from, nb_to, 1, (u64*)d_counts, nullptr, nullptr);
+    const bool items32 = pl.kernel == CK_AND_ROWS || pl.kernel == CK_GAPCOUNT || pl.kernel == CK_GENERAL;      // (these take the item count as 32 bits)
+    if (items32 && pl.nitems > 0xFFFFFFF0ull) { g_last_error = "too many (column, group) items in one run"; return BMX_ERR_RANGE; }
+    switch (pl.kernel) {
+    case CK_COLL_APPLY: return coll_launch(COLL_AND_COUNT, ctx, ca, cs, nb_from, nb_to, 1, (u64*)d_counts, nullptr, nullptr, 0u, 0xFFFFFFFFu);
+    case CK_COLL_MEMBERS:
+        return coll_members_launch(CM_AND_COUNT, ctx, ca, cs, (const u32*)p->cm_buf, gv ? gv->cgroups : (const CollGroup*)((const char*)p->cm_buf + p->cm_groups_off),
+                                   ngroups, nb_from, nb_to, 1, (u64*)d_counts, nullptr, nullptr);
+    case CK_STAGED: {
+        auto fn = pl.slots == 8 ? k_pipe_counts_staged<8> : k_pipe_counts_staged<16>;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(fn, dim3(pl.ncols), dim3(pl.slots * 64), pl.lds, ctx->stream,
+                           (const u64* const*)p->d_udesc, (const u32*)p->d_unblk, p->nplanes, gv ? gv->gmask : (const u32*)p->d_gmask, gv ? gv->gskip : (const u32*)p->d_gskip,
+                           ngroups, nb_from, pl.ncols, ctx->xcd_swz, (u64*)d_counts);
+        break;
     }
-    {
-        // many groups over few distinct vectors: every plane block is re-used >= 8 times per column
-        bool reuse = p->ngroups >= 32 && (uint64_t)p->n_ops >= 8ull * p->nplanes;
-        bool use_staged = p->staged_ok && (ctx->pipe_staged == 1 || (ctx->pipe_staged < 0 && reuse));
-        if (use_staged) {
-            size_t lds = (size_t)ctx->pipe_slots * 8192;
-#define LAUNCH_STG(S) do { \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pipe_counts_staged<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_counts_staged<S>), dim3(nb_to - nb_from), dim3(S * 64), lds, ctx->stream, \
-                               (const u64* const*)p->d_udesc, (const u32*)p->d_unblk, p->nplanes, gv ? gv->gmask : (const u32*)p->d_gmask, gv ? gv->gskip : (const u32*)p->d_gskip, \
-                               ngroups, nb_from, nb_to - nb_from, ctx->xcd_swz, (u64*)d_counts); } while (0)
-            if (ctx->pipe_slots == 8) LAUNCH_STG(8); else LAUNCH_STG(16);
-#undef LAUNCH_STG
-            KCHK();
-            return BMX_OK;
-        }
-    }
-    if (use_split(ctx, p, nitems64)) {
-        // few (column, group) items with long operand lists: 8 waves share an item (k_pipe_split, counts mode)
-        size_t lds = (size_t)SPLIT_WAVES * 8192;
+    case CK_SPLIT: {
         auto fn = k_pipe_split<2, SPLIT_WAVES>;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(fn, dim3((u32)nitems64), dim3(SPLIT_WAVES * 64), lds, ctx->stream,
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(fn, dim3((u32)pl.nitems), dim3(SPLIT_WAVES * 64), pl.lds, ctx->stream,
                            (const u64*)p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from, nb_to, 0, (u64*)d_counts,
                            0, (uint4*)nullptr, (u64*)nullptr, (BlockStat*)nullptr);
-        KCHK();
-        return BMX_OK;
+        break;
     }
-    if (!p->has_gap) {
-        // bit-block-only fast path: (column, group, slice) items
-        // Launch plan (pipe_plan): the run is issued as a sequence of launches over column WINDOWS of at most one
-        // machine-load of waves each.  Inside a window every wave is in flight at once and the whole chip walks
-        // the operand list in step: at any moment HBM serves ONE contiguous stretch of one operand slab (open-page
-        // locality) instead of 256 unrelated streams, which is what a single launch over all columns degenerates
-        // into after its first round of workgroups (measured: +5 % on the headline, tools/chunk_probe.py; a
-        // 1,908-column shard = one window runs at a higher rate than the full-size steady state).
-        u32 rows, wg, unroll, window;
-        pipe_plan(ctx, nitems64, ngroups, rows, wg, unroll, window);
-        u32 parts = 8u / rows;
-        if (nitems64 * parts > 0xFFFFFFF0ull) { g_last_error = "too many work items in one run"; return BMX_ERR_RANGE; }
-        pipe_bits_fn fn = pipe_bits_kernel(rows, unroll, ctx->pipe_nt != 0, wg);
+    case CK_BITS: {
+        if (pl.nitems * pl.parts > 0xFFFFFFF0ull) { g_last_error = "too many work items in one run"; return BMX_ERR_RANGE; }
+        pipe_bits_fn fn = pipe_bits_kernel(pl.rows, pl.unroll, pl.nt, pl.wg);
         if (!fn) { g_last_error = "this (pipe_rows, pipe_unroll, pipe_nt, pipe_wg) shape is not compiled into the library"; return BMX_ERR_BADARG; }
-        u32 wpb = wg / 64u;
-        u32 ncols = nb_to - nb_from;
-        u32 nwin = window ? (ncols + window - 1u) / window : 1u;
-        u32 per = (ncols + nwin - 1u) / nwin;                      // even split: no short last window
-        for (u32 c0 = 0; c0 < ncols; c0 += per) {
-            u32 cols = std::min(per, ncols - c0);
-            u32 nitems = cols * ngroups * parts, grid = (nitems + wpb - 1) / wpb;
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(wg), (size_t)ctx->pipe_lds, ctx->stream,
+        const u32 wpb = pl.wg / 64u;
+        for (u32 c0 = 0; c0 < pl.ncols; c0 += pl.win.per) {
+            u32 nitems = std::min(pl.win.per, pl.ncols - c0) * ngroups * pl.parts;
+            hipLaunchKernelGGL(fn, dim3((nitems + wpb - 1) / wpb), dim3(pl.wg), pl.lds, ctx->stream,
                                (const u64*)p->d_dmat, row_off, and_n, p->col_stride, ngroups, nb_from + c0, nitems, ctx->xcd_swz, (u64*)d_counts);
             KCHK();
         }
         return BMX_OK;
     }
-    if (nitems64 > 0xFFFFFFF0ull) { g_last_error = "too many (column, group) items in one run"; return BMX_ERR_RANGE; }
-    if (use_and_rows(ctx, p)) {
-        // every operand block is GAP (or NULL / FULL): the union of the operands' 0-runs read straight from their slabs
-        // (and_rows_ipw: several consecutive items -- arg-groups of one column -- per workgroup.  Measured on 16 groups x 2 .. 64 operands
-        // over 1e9-bit vectors: 1, 4 and 8 items per workgroup run within 2 % of each other -- such a run is bound by the chain of
-        // dependent round trips inside an item (row header, entries, pieces, fold), not by the dispatch rate -- so the default is 1)
-        const u32 ipw = ctx->and_rows_ipw > 0 ? (u32)ctx->and_rows_ipw : 1u;
-        hipLaunchKernelGGL(and_rows_kernel<AR_COUNT>(ctx), dim3((u32)((nitems64 + ipw - 1u) / ipw)), dim3((u32)ctx->and_rows_wg), 0, ctx->stream,
-                           (const u64*)p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from, (u32)nitems64, ctx->xcd_swz, (u64*)d_counts,
-                           (uint4*)nullptr, (u64*)nullptr, (BlockStat*)nullptr, 0u, 0xFFFFFFFFu, and_rows_diag_bits(), ipw);
-        KCHK();
-        return BMX_OK;
-    }
-    if (use_gapcount(ctx, p)) {
-        // every operand block is GAP (or NULL / FULL): the counting formulation, one 1024-thread workgroup per (column, group)
-        size_t lds = (size_t)(16384 * 2 + 2048) * 4;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pipe_counts_gapcount<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_counts_gapcount<false>), dim3((u32)nitems64), dim3(1024), lds, ctx->stream,
-                           p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from, (u32)nitems64, (u64*)d_counts,
+    case CK_AND_ROWS:
+        hipLaunchKernelGGL(and_rows_kernel<AR_COUNT>(ctx), dim3((u32)((pl.nitems + pl.ar_ipw - 1u) / pl.ar_ipw)), dim3(pl.ar_wg), pl.lds, ctx->stream,
+                           (const u64*)p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from, (u32)pl.nitems, ctx->xcd_swz, (u64*)d_counts,
+                           (uint4*)nullptr, (u64*)nullptr, (BlockStat*)nullptr, 0u, 0xFFFFFFFFu, and_rows_diag_bits(), pl.ar_ipw);
+        break;
+    case CK_GAPCOUNT:
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pipe_counts_gapcount<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_counts_gapcount<false>), dim3((u32)pl.nitems), dim3(1024), pl.lds, ctx->stream,
+                           p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from, (u32)pl.nitems, (u64*)d_counts,
                            (uint4*)nullptr, (u64*)nullptr, (BlockStat*)nullptr, 0u, 0xFFFFFFFFu);
-        KCHK();
+        break;
+    case CK_GENERAL: {
+        auto fn = k_pipe_counts<1>;
+        if (pl.unroll != 1) fn = pl.unroll == 2 ? k_pipe_counts<2> : k_pipe_counts<4>;
+        for (u32 c0 = 0; c0 < pl.ncols; c0 += pl.win.per) {
+            u32 nitems = std::min(pl.win.per, pl.ncols - c0) * ngroups;
+            hipLaunchKernelGGL(fn, dim3((nitems + 3) / 4), dim3(256), pl.lds, ctx->stream,
+                               p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from + c0, nitems, ctx->xcd_swz, (u64*)d_counts);
+            KCHK();
+        }
         return BMX_OK;
     }
-    // general kernel (GAP operands present): ONE launch unless pipe_window asks for windows.  Measured (256-way AND, mixed
-    // 1 % and all-GAP 0.3 %): 2,048-column windows cost 19-38 %, 3,072 are neutral -- columns with GAP operands take
-    // unequal time, so a window boundary idles most of the chip while the slowest columns finish.
-    size_t lds = 4 * 2048 * 4;
-    u32 ncols = nb_to - nb_from;
-    u32 window = ctx->pipe_window > 0 ? (u32)ctx->pipe_window : 0u;
-    u32 nwin = window ? (ncols + window - 1u) / window : 1u;
-    u32 per = (ncols + nwin - 1u) / nwin;
-    for (u32 c0 = 0; c0 < ncols; c0 += per) {
-        u32 cols = std::min(per, ncols - c0);
-        u32 nitems = cols * ngroups;
-        u32 grid = (nitems + 3) / 4;
-#define LAUNCH_PIPE(U) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_counts<U>), dim3(grid), dim3(256), lds, ctx->stream, \
-        p->d_dmat, row_off, and_n, sub_n, p->col_stride, ngroups, nb_from + c0, nitems, ctx->xcd_swz, (u64*)d_counts)
-        switch (ctx->pipe_unroll) {
-        case 1: LAUNCH_PIPE(1); break;
-        case 2: LAUNCH_PIPE(2); break;
-        default: LAUNCH_PIPE(4); break;
-        }
-#undef LAUNCH_PIPE
-        KCHK();
     }
+    KCHK();
     return BMX_OK;
 }
 
+extern "C" {
+
+// the plan as text: what the benchmark's roofline.kernel / kernel_plan and the tests' "which path ran" asserts read.  The collections are
+// those the last run resolved, if still in force: looked up only (nothing is resolved, built or allocated, the LRU tick stays)
 int bmx_pipeline_describe(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, char* buf, size_t buf_len, uint32_t* n_launches)
 { ABI_TRY
     ARGCHK(ctx && p && p->ctx == ctx && buf && buf_len > 0);
     if (n_launches) *n_launches = 1;
     int rc = pipe_range(p, nb_from, nb_to); if (rc) return rc;
-    u64 nitems64 = (u64)(nb_to - nb_from) * p->ngroups;
-    bool reuse = p->ngroups >= 32 && (uint64_t)p->n_ops >= 8ull * p->nplanes;
-    if (!p->h_uids.empty() && ctx->gap_pack != 0 && p->cm_gen == ctx->coll_gen && coll_by_id(ctx, p->cm_a_id) && (!p->cm_s_id || coll_by_id(ctx, p->cm_s_id))) {
-        if (p->cm_full) snprintf(buf, buf_len, "k_coll_apply<AND_COUNT,512> x 1 launch, %llu workgroups (packed collection of the operand set)", (unsigned long long)nitems64);
-        else snprintf(buf, buf_len, "k_coll_members<AND_COUNT> x 1 launch, a wave per (column, group): %u x %u items (members of a packed collection)", nb_to - nb_from, p->ngroups);
+    bmx_coll *ca = nullptr, *cs = nullptr;
+    if (!p->h_uids.empty() && ctx->gap_pack != 0 && p->cm_gen == ctx->coll_gen) (void)pipe_colls_valid(ctx, p, &ca, &cs);
+    const CountsPlan pl = counts_plan(ctx, p, nb_from, nb_to, p->ngroups, coll_serve(p, ca));
+    switch (pl.kernel) {
+    case CK_COLL_APPLY: snprintf(buf, buf_len, "k_coll_apply<AND_COUNT,512> x 1 launch, %llu workgroups (packed collection of the operand set)", pl.nitems); break;
+    case CK_COLL_MEMBERS: snprintf(buf, buf_len, "k_coll_members<AND_COUNT> x 1 launch, a wave per (column, group): %u x %u items (members of a packed collection)", pl.ncols, pl.ngroups); break;
+    case CK_STAGED: snprintf(buf, buf_len, "k_pipe_counts_staged<%u> x 1 launch, %u workgroups", pl.slots, pl.ncols); break;
+    case CK_SPLIT: snprintf(buf, buf_len, "k_pipe_split<2,%d> x 1 launch, %llu workgroups", SPLIT_WAVES, pl.nitems); break;
+    case CK_AND_ROWS: snprintf(buf, buf_len, "k_agg_and_rows<COUNT,%u,%u> x 1 launch, %llu workgroups", pl.ar_wg, pl.ar_depth, pl.nitems); break;
+    case CK_GAPCOUNT: snprintf(buf, buf_len, "k_pipe_counts_gapcount x 1 launch, %llu workgroups", pl.nitems); break;
+    case CK_GENERAL:
+        if (pl.win.nwin == 1) snprintf(buf, buf_len, "k_pipe_counts<%u> x 1 launch", pl.unroll);
+        else snprintf(buf, buf_len, "k_pipe_counts<%u> x %u launches of <= %u columns", pl.unroll, pl.win.nwin, pl.win.per);
+        break;
+    case CK_BITS:
+        snprintf(buf, buf_len, "k_pipe_counts_bits2<%u,%s,%u,%u> x %u launch%s of <= %u columns", pl.unroll, pl.nt ? "true" : "false",
+                 pl.wg, pl.rows, pl.win.nwin, pl.win.nwin == 1 ? "" : "es", pl.win.per);
+        break;
     }
-    else if (p->staged_ok && (ctx->pipe_staged == 1 || (ctx->pipe_staged < 0 && reuse)))
-        snprintf(buf, buf_len, "k_pipe_counts_staged<%d> x 1 launch, %u workgroups", ctx->pipe_slots, nb_to - nb_from);
-    else if (use_split(ctx, p, nitems64))
-        snprintf(buf, buf_len, "k_pipe_split<2,%d> x 1 launch, %llu workgroups", SPLIT_WAVES, (unsigned long long)nitems64);
-    else if (use_and_rows(ctx, p))
-        snprintf(buf, buf_len, "k_agg_and_rows<COUNT,%d,%d> x 1 launch, %llu workgroups", ctx->and_rows_wg, ctx->and_rows_depth, (unsigned long long)nitems64);
-    else if (use_gapcount(ctx, p))
-        snprintf(buf, buf_len, "k_pipe_counts_gapcount x 1 launch, %llu workgroups", (unsigned long long)nitems64);
-    else if (p->has_gap)
-        snprintf(buf, buf_len, "k_pipe_counts<%d> x 1 launch", ctx->pipe_unroll == 1 ? 1 : ctx->pipe_unroll == 2 ? 2 : 4);
-    else {
-        u32 rows, wg, unroll, window;
-        pipe_plan(ctx, nitems64, p->ngroups, rows, wg, unroll, window);
-        u32 ncols = nb_to - nb_from, nwin = (window && ncols) ? (ncols + window - 1u) / window : 1u;
-        u32 per = nwin ? (ncols + nwin - 1u) / nwin : 0u;
-        snprintf(buf, buf_len, "k_pipe_counts_bits2<%u,%s,%u,%u> x %u launch%s of <= %u columns", unroll, ctx->pipe_nt ? "true" : "false",
-                 wg, rows, nwin, nwin == 1 ? "" : "es", per);
-        if (n_launches) *n_launches = nwin;
-    }
+    if (n_launches) *n_launches = pl.win.nwin;
     return BMX_OK;
 ABI_END }
 
@@ -2458,6 +2468,30 @@ ABI_END }
 
 } // extern "C"
 
+// What both counts runs under a search limit set up before their first window: the collections in force, resolved once and pinned
+// (the member table captured here must stay what the windows resolve: no eviction mid-run), and ONE device block: per-group totals,
+// the window's counts (u64) | own_words x ngroups of the variant's own | (CollGroup member ranges, 16-aligned) | (mask_words x ngroups)
+struct LimitScratch {
+    CollPin pin; DevBuf buf; bool have_cg = false, have_masks = false;
+    u64 *d_tot = nullptr, *d_cc = nullptr; u32 *d_own = nullptr, *d_masks = nullptr, *d_end = nullptr; CollGroup* d_cg = nullptr;
+    explicit LimitScratch(bmx_ctx* ctx) : buf(ctx) {}
+};
+static int limit_scratch(bmx_ctx* ctx, bmx_pipeline* p, bool may_build, size_t own_words, size_t mask_words, LimitScratch* s)
+{
+    int rc; const size_t ng = p->ngroups; bmx_coll *ca = nullptr, *cs = nullptr;
+    if (!p->h_uids.empty() && (rc = pipe_resolve_colls(ctx, p, may_build, &ca, &cs))) return rc;
+    s->pin.pin(ca, cs);
+    s->have_cg = ca && !p->cm_full && p->cm_buf; s->have_masks = p->staged_ok && p->d_gmask && p->d_gskip;
+    const size_t words = ng * (2 + 2 + own_words + (s->have_cg ? 4 : 0) + (s->have_masks ? mask_words : 0)) + 16;
+    if ((rc = dmalloc(ctx, &s->buf.p, words * 4))) return rc;
+    s->d_tot = (u64*)s->buf.p; s->d_cc = s->d_tot + ng; s->d_own = (u32*)(s->d_cc + ng);
+    u32* q = (u32*)(((uintptr_t)(s->d_own + own_words * ng) + 15u) & ~(uintptr_t)15u);
+    if (s->have_cg) { s->d_cg = (CollGroup*)q; q += ng * 4; }
+    if (s->have_masks) { s->d_masks = q; q += ng * mask_words; }
+    s->d_end = q;
+    return BMX_OK;
+}
+
 // The counts run under pipeline::set_search_count_limit (src/bmaggregator.h:255, honoured PER ARG-GROUP at :1362-1367: a group
 // whose count has reached the limit is skipped on every following block -- "can find more, cannot find less").  Here: ascending
 // launch windows of block columns (each 4 x the one before, as find_first_and_sub walks them); the per-group totals stay on the
@@ -2466,51 +2500,37 @@ ABI_END }
 // >= min(limit, its true count) and never more than its true count; h_stop[g] = the column at which it stopped.
 static int limit_counts_run(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* counts_out)
 {
-    int rc;
-    uint32_t f = nb_from, t = nb_to;
-    if ((rc = pipe_range(p, f, t))) return rc;
-    const u32 ng = p->ngroups, ncols = t - f;
+    int rc = pipe_range(p, nb_from, nb_to); if (rc) return rc;
+    const u32 ng = p->ngroups, ncols = nb_to - nb_from;
     p->h_win_groups.clear(); p->h_stop.assign(ng, 0xFFFFFFFFu);
     u32 w = std::max<u32>(ncols / 64u, 16u), planned = 0;
     for (u32 c = 0, ww = w; c < ncols; c += ww, ww *= 4u) ++planned;
     p->last_windows_planned = std::max(planned, 1u); p->last_windows = 0;
     if (counts_out) for (u32 g = 0; g < ng; ++g) counts_out[g] = 0;
     if (!ncols) return BMX_OK;
-    // collections / staged tables in force (resolved once, before the first window)
-    bmx_coll *ca = nullptr, *cs = nullptr;
-    if (!p->h_uids.empty() && (rc = pipe_resolve_colls(ctx, p, true, &ca, &cs))) return rc;
-    CollPin pin; pin.pin(ca, cs);                              // (the member table captured below must stay what the windows resolve: no eviction mid-run)
-    const bool have_cg = ca && !p->cm_full && p->cm_buf;
-    const bool have_masks = p->staged_ok && p->d_gmask && p->d_gskip;
+    // device state: totals, the window's compact counts | stop columns, two active lists, the compacted tables | (member ranges) |
+    // (plane masks, gskip) | the number of groups left
     const size_t nch = std::max<u32>(p->nchunks, 1u);
-    // device state: totals, the window's compact counts, stop columns, two active lists, the compacted tables
-    const size_t words = (size_t)ng * (2 + 2 + 1 + 2 + 3 + (have_cg ? 4 : 0) + (have_masks ? nch + 1 : 0)) + 16;
-    DevBuf buf(ctx);
-    if ((rc = dmalloc(ctx, &buf.p, words * 4))) return rc;
-    u64* d_tot = (u64*)buf; u64* d_cc = d_tot + ng;
-    u32* d_stop = (u32*)(d_cc + ng); u32* d_act[2] = {d_stop + ng, d_stop + 2 * (size_t)ng};
+    LimitScratch s(ctx);
+    if ((rc = limit_scratch(ctx, p, true, 1 + 2 + 3, nch + 1, &s))) return rc;
+    u64* d_tot = s.d_tot; u64* d_cc = s.d_cc; CollGroup* d_cg = s.d_cg;
+    u32* d_stop = s.d_own; u32* d_act[2] = {d_stop + ng, d_stop + 2 * (size_t)ng};
     u32* d_ro = d_act[1] + ng; u32* d_an = d_ro + ng; u32* d_sn = d_an + ng;
-    u32* q = d_sn + ng;
-    q = (u32*)(((uintptr_t)q + 15u) & ~(uintptr_t)15u);
-    CollGroup* d_cg = nullptr; u32* d_gm = nullptr; u32* d_gs = nullptr;
-    if (have_cg) { d_cg = (CollGroup*)q; q += (size_t)ng * 4; }
-    if (have_masks) { d_gm = q; q += (size_t)ng * nch; d_gs = q; q += ng; }
-    u32* d_nact = q;
+    u32* d_gm = s.d_masks; u32* d_gs = s.have_masks ? d_gm + (size_t)ng * nch : nullptr; u32* d_nact = s.d_end;
     hipError_t e = hipMemsetAsync(d_tot, 0, (size_t)ng * 8, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_stop, 0xFF, (size_t)ng * 4, ctx->stream);
     if (e != hipSuccess) return fail_hip(e, "limit_counts_run", __LINE__);
     LimitTables lt{p->d_meta, p->d_meta + ng, p->d_meta + 2 * (size_t)ng, d_ro, d_an, d_sn,
-                   have_cg ? (const CollGroup*)((const char*)p->cm_buf + p->cm_groups_off) : nullptr, d_cg,
-                   have_masks ? (const u32*)p->d_gmask : nullptr, have_masks ? (const u32*)p->d_gskip : nullptr, d_gm, d_gs, (u32)nch};
+                   s.have_cg ? (const CollGroup*)((const char*)p->cm_buf + p->cm_groups_off) : nullptr, d_cg,
+                   s.have_masks ? (const u32*)p->d_gmask : nullptr, s.have_masks ? (const u32*)p->d_gskip : nullptr, d_gm, d_gs, (u32)nch};
     GroupView gv{d_ro, d_an, d_sn, ng, d_gm, d_gs, d_cg};
     u32 n_active = ng; int cur = 0; bool first = true;
     for (u32 c = 0; c < ncols && n_active && !rc; c += w, w *= 4u) {
         const u32 c1 = (u32)std::min<u64>((u64)c + w, ncols);
         gv.ngroups = n_active;
-        rc = pipeline_run_counts_impl(ctx, p, f + c, f + c1, d_cc, false, first ? nullptr : &gv);
-        if (rc) break;
+        if ((rc = pipeline_run_counts_impl(ctx, p, nb_from + c, nb_from + c1, d_cc, false, first ? nullptr : &gv))) break;
         hipLaunchKernelGGL(k_limit_step, dim3(1), dim3(1024), 0, ctx->stream, d_tot, (const u64*)d_cc, first ? (const u32*)nullptr : (const u32*)d_act[cur], n_active,
-                           p->search_limit, f + c1, d_stop, d_act[cur ^ 1], lt, d_nact, ctx->h_small + 60);
+                           p->search_limit, nb_from + c1, d_stop, d_act[cur ^ 1], lt, d_nact, ctx->h_small + 60);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);        // (the word in pinned memory is all the host reads)
         if (e != hipSuccess) { rc = fail_hip(e, "k_limit_step", __LINE__); break; }
@@ -2535,38 +2555,24 @@ static int limit_counts_run(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
 static int limit_counts_run_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts)
 {
     int rc = set_dev(ctx); if (rc) return rc;
-    uint32_t f = nb_from, t = nb_to;
-    if ((rc = pipe_range(p, f, t))) return rc;
-    const u32 ng = p->ngroups, ncols = t - f;
+    if ((rc = pipe_range(p, nb_from, nb_to))) return rc;
+    const u32 ng = p->ngroups, ncols = nb_to - nb_from;
     HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)std::max(ng, 1u) * 8, ctx->stream));
     if (!ncols || !ng) return BMX_OK;
-    bmx_coll *ca = nullptr, *cs = nullptr;
-    if (!p->h_uids.empty() && (rc = pipe_resolve_colls(ctx, p, false, &ca, &cs))) return rc;
-    CollPin pin; pin.pin(ca, cs);
-    const bool have_cg = ca && !p->cm_full && p->cm_buf;
-    const bool have_masks = p->staged_ok && p->d_gmask && p->d_gskip;
-    // totals, the window's counts, row offsets, (member ranges), (gskip)
-    const size_t words = (size_t)ng * (2 + 2 + 1 + (have_cg ? 4 : 0) + (have_masks ? 1 : 0)) + 16;
-    DevBuf buf(ctx);                                               // (pooled: handed only to work enqueued behind this run)
-    if ((rc = dmalloc(ctx, &buf.p, words * 4))) return rc;
-    u64* d_tot = (u64*)buf; u64* d_cc = d_tot + ng;
-    u32* d_ro = (u32*)(d_cc + ng);
-    u32* q = d_ro + ng;
-    q = (u32*)(((uintptr_t)q + 15u) & ~(uintptr_t)15u);
-    CollGroup* d_cg = nullptr; u32* d_gs = nullptr;
-    if (have_cg) { d_cg = (CollGroup*)q; q += (size_t)ng * 4; }
-    if (have_masks) { d_gs = q; q += ng; }
+    // totals, the window's counts | row offsets | (member ranges) | (gskip).  Pooled: handed only to work enqueued behind this run
+    LimitScratch s(ctx);
+    if ((rc = limit_scratch(ctx, p, false, 1, 1, &s))) return rc;
+    u64* d_tot = s.d_tot; u64* d_cc = s.d_cc; u32* d_ro = s.d_own; CollGroup* d_cg = s.d_cg; u32* d_gs = s.d_masks;
     hipError_t e = hipMemsetAsync(d_tot, 0, (size_t)ng * 8, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ro, p->d_meta, (size_t)ng * 4, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess && have_cg) e = hipMemcpyAsync(d_cg, (const char*)p->cm_buf + p->cm_groups_off, (size_t)ng * sizeof(CollGroup), hipMemcpyDeviceToDevice, ctx->stream);
-    if (e == hipSuccess && have_masks) e = hipMemcpyAsync(d_gs, p->d_gskip, (size_t)ng * 4, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && s.have_cg) e = hipMemcpyAsync(d_cg, (const char*)p->cm_buf + p->cm_groups_off, (size_t)ng * sizeof(CollGroup), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && s.have_masks) e = hipMemcpyAsync(d_gs, p->d_gskip, (size_t)ng * 4, hipMemcpyDeviceToDevice, ctx->stream);
     if (e != hipSuccess) return fail_hip(e, "limit_counts_run_dev", __LINE__);
-    GroupView gv{d_ro, p->d_meta + ng, p->d_meta + 2 * (size_t)ng, ng, have_masks ? (const u32*)p->d_gmask : nullptr, d_gs, d_cg};
+    GroupView gv{d_ro, p->d_meta + ng, p->d_meta + 2 * (size_t)ng, ng, s.have_masks ? (const u32*)p->d_gmask : nullptr, d_gs, d_cg};
     u32 w = std::max<u32>(ncols / 64u, 16u);
     for (u32 c = 0; c < ncols && !rc; c += w, w *= 4u) {
         const u32 c1 = (u32)std::min<u64>((u64)c + w, ncols);
-        rc = pipeline_run_counts_impl(ctx, p, f + c, f + c1, d_cc, false, &gv);
-        if (rc) break;
+        if ((rc = pipeline_run_counts_impl(ctx, p, nb_from + c, nb_from + c1, d_cc, false, &gv))) break;
         hipLaunchKernelGGL(k_limit_null, dim3((ng + 255u) / 256u), dim3(256), 0, ctx->stream, d_tot, (const u64*)d_cc, ng, p->search_limit, p->null_row_off,
                            d_ro, d_cg, d_gs, c1 >= ncols ? (u64*)d_counts : (u64*)nullptr);
         e = hipGetLastError();
@@ -2585,6 +2591,13 @@ int bmx_pipeline_last_window_groups(const bmx_pipeline* p, uint32_t* out, uint32
     for (uint32_t i = 0; i < have && i < cap; ++i) out[i] = p->h_win_groups[i];
     if (n) *n = have;
     return BMX_OK;
+ABI_END }
+
+int bmx_pipeline_run_counts_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* d_counts)
+{ ABI_TRY
+    ARGCHK(ctx && p && p->ctx == ctx && d_counts);
+    if (p->search_limit != ~0ull) return limit_counts_run_dev(ctx, p, nb_from, nb_to, d_counts);
+    return pipeline_run_counts_impl(ctx, p, nb_from, nb_to, d_counts, false);
 ABI_END }
 
 int bmx_pipeline_run_counts(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* counts_out)
@@ -3315,8 +3328,7 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
         auto tiled = ctx->or_tile == 0 ? k_agg_or_gap_tiled<1, 1> : ctx->or_tile == 2 ? k_agg_or_gap_tiled<1, 2> : k_agg_or_gap_tiled<0, 1>;
 #endif
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tiled), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        u32 win = ctx->or_window <= 0 ? ntiles : (u32)ctx->or_window;        // windows measured: no gain here
-        u32 nwin = (ntiles + win - 1) / win, per = (ntiles + nwin - 1) / nwin;
+        const u32 per = even_windows(ntiles, ctx->or_window <= 0 ? 0u : (u32)ctx->or_window).per;      // windows measured: no gain here
         for (u32 t0 = 0; t0 < ntiles; t0 += per) {
             hipLaunchKernelGGL(tiled, dim3(std::min(per, ntiles - t0)), dim3(1024), lds, ctx->stream,
                                ops.d_descs, ops.d_nblk, (u32)n, ncols, opt_compress, v->d_bits, v->d_desc, st, t0);
@@ -3345,24 +3357,32 @@ static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int op
 // one (column-per-wave) materialising aggregation of group g of a pipeline.  Bit-block operands only and enough columns:
 // the launch plan of the headline kernel (windows of one 640-thread workgroup per CU, 4 blocks in flight per wave);
 // otherwise one launch of 256-thread workgroups (GAP operands park the accumulator in LDS: 8 KiB per wave).
-static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, bmx_vec* v, BlockStat* st, uint32_t nb_from, uint32_t nb_to)
+// may_split: few columns with a long operand list take k_pipe_split (8 waves per column); bmx_agg_and_sub sets it, results pipelines do not.
+static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, bmx_vec* v, BlockStat* st, uint32_t nb_from, uint32_t nb_to, bool may_split = false)
 {
     const u64* rows = p->d_dmat + p->h_row_off[g];
-    const u32* an = p->d_meta + p->ngroups + g;
-    const u32* sn = p->d_meta + 2 * p->ngroups + g;
+    const u32 *an = p->d_meta + p->ngroups + g, *sn = p->d_meta + 2 * p->ngroups + g;
     const u32 ncols = p->ncols;
-    hipError_t e = hipSuccess;
-    if (ncols && use_and_rows(ctx, p, (uint64_t)p->h_and_n[g] + p->h_sub_n[g])) {
+    hipError_t e = hipSuccess; const char* what = "k_agg_and_sub";
+    if (may_split && use_split(ctx, p, ncols)) {
+        size_t lds = (size_t)SPLIT_WAVES * 8192; auto fn = k_pipe_split<2, SPLIT_WAVES>; what = "k_pipe_split";
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(fn, dim3(ncols), dim3(SPLIT_WAVES * 64), lds, ctx->stream,
+                               rows, p->d_meta /* row_off[0] = 0: rows already points at group g */, an, sn,
+                               p->col_stride, 1u, 0u, ncols, 1, (u64*)nullptr, 1, v->d_bits, v->d_desc, st);
+            e = hipGetLastError();
+        }
+    } else if (ncols && use_and_rows(ctx, p, (uint64_t)p->h_and_n[g] + p->h_sub_n[g])) {
         // GAP-only operands: the union of 0-runs over the operands' own slabs, result block stored (bmx_kernels9.h)
+        what = "k_agg_and_rows";
         hipLaunchKernelGGL(and_rows_kernel<AR_STORE>(ctx), dim3(ncols), dim3((u32)ctx->and_rows_wg), 0, ctx->stream,
                            rows, p->d_meta /* row_off[0] = 0: rows already points at group g */, an, sn, p->col_stride, 1u, 0u, ncols, ctx->xcd_swz, (u64*)nullptr,
                            v->d_bits, v->d_desc, st, nb_from, nb_to, 0, 1u);
         e = hipGetLastError();
-        return e == hipSuccess ? BMX_OK : fail_hip(e, "k_agg_and_rows", __LINE__);
-    }
-    if (ncols && use_gapcount(ctx, p, p->h_and_n[g])) {
+    } else if (ncols && use_gapcount(ctx, p, p->h_and_n[g])) {
         // GAP-only operands, a long list: the counting formulation, one 1024-thread workgroup per column, result block stored
-        size_t lds = (size_t)(16384 * 2 + 2048) * 4;
+        size_t lds = (size_t)(16384 * 2 + 2048) * 4; what = "k_pipe_counts_gapcount";
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_pipe_counts_gapcount<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pipe_counts_gapcount<true>), dim3(ncols), dim3(1024), lds, ctx->stream,
@@ -3370,9 +3390,7 @@ static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, b
                                v->d_bits, v->d_desc, st, nb_from, nb_to);
             e = hipGetLastError();
         }
-        return e == hipSuccess ? BMX_OK : fail_hip(e, "k_pipe_counts_gapcount", __LINE__);
-    }
-    if (!p->has_gap && ncols >= 2560u && ctx->pipe_window >= 0 && (ctx->pipe_wg == 0 || ctx->pipe_wg == 640)) {
+    } else if (!p->has_gap && ncols >= 2560u && ctx->pipe_window >= 0 && (ctx->pipe_wg == 0 || ctx->pipe_wg == 640)) {
         // (640 threads = 10 waves per CU; 512 measured: 4.98 against 4.86 ms on the 256 x 1e9-bit combine_and.  Four operand
         // blocks in flight per wave need ~180 VGPRs, more than the 168 a 640-thread workgroup leaves a wave: <4, 640> spilled
         // 80 B per lane to scratch.  agg_shape 0 = three blocks in flight at 640 threads (143 VGPRs), 1 = four at
@@ -3380,8 +3398,7 @@ static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, b
         const bool s512 = ctx->agg_shape == 1;
         const u32 wpb = s512 ? 8u : 10u, wgs = wpb * 64u;
         const u32 cap = ctx->pipe_window > 0 ? (u32)ctx->pipe_window : pipe_window_cap(wgs);
-        u32 nwin = (ncols + cap - 1u) / cap, per = (ncols + nwin - 1u) / nwin;
-        per = (per + wpb - 1u) / wpb * wpb;                               // whole workgroups
+        const u32 per = (even_windows(ncols, cap).per + wpb - 1u) / wpb * wpb;      // whole workgroups
         for (u32 c0 = 0; c0 < ncols && e == hipSuccess; c0 += per) {
             u32 n = std::min(per, ncols - c0);
             if (s512) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_agg_and_sub<4, 512>), dim3((n + wpb - 1u) / wpb), dim3(512), 0, ctx->stream,
@@ -3398,7 +3415,18 @@ static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, b
                            rows, an, sn, p->col_stride, ncols, 1, ctx->xcd_swz, v->d_bits, v->d_desc, st, nb_from, nb_to, 0u);
         e = hipGetLastError();
     }
-    return e == hipSuccess ? BMX_OK : fail_hip(e, "k_agg_and_sub", __LINE__);
+    return e == hipSuccess ? BMX_OK : fail_hip(e, what, __LINE__);
+}
+
+// The tail of every path of bmx_agg_and_sub: lay the stored blocks out (result_finish synchronises), or wait for what a failed launch
+// left on the stream; then hand the result over.  The caller's scope-owned temporaries (tables, pipeline) go behind that wait.
+static int agg_and_sub_finish(bmx_ctx* ctx, int rc, Owned<bmx_vec>& v, BlockStat* st, u32* offs, bmx_vec** result, int* any)
+{
+    if (!rc) rc = result_finish(ctx, v.get(), st, offs); else (void)hipStreamSynchronize(ctx->stream);
+    if (rc) return rc;
+    if (any) *any = vec_any_block(v.get());
+    *result = v.release();
+    return BMX_OK;
 }
 
 extern "C" {
@@ -3421,13 +3449,7 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
         if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = direct_table(ctx, &ops, d_tab))) return rc;
         if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
         rc = direct_launch(DIRECT_AND_SUB, ctx, ops, n_and, n_sub, 0u, ncols, 1, v.get(), st, 0, 0u, 0u);
-        if (!rc) rc = result_finish(ctx, v.get(), st, offs);              // synchronises
-        else (void)hipStreamSynchronize(ctx->stream);
-        d_tab.reset();
-        if (rc) return rc;
-        if (any) *any = vec_any_block(v.get());
-        *result = v.release();
-        return BMX_OK;
+        return agg_and_sub_finish(ctx, rc, v, st, offs, result, any);
     }
     {
         // GAP-only operands held by packed collections: the whole column regions (the lists name every vector of their
@@ -3454,38 +3476,15 @@ int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
                 rc = coll_members_upload(ctx, ma, ms, d_buf, &d_midx, &d_groups);
                 if (!rc) rc = coll_members_launch(CM_AND_STORE, ctx, ca, cs, d_midx, d_groups, 1u, 0u, ncols, 1, nullptr, v.get(), st);
             }
-            if (!rc) rc = result_finish(ctx, v.get(), st, offs);
-            else (void)hipStreamSynchronize(ctx->stream);
-            d_buf.reset();
-            if (rc) return rc;
-            if (any) *any = vec_any_block(v.get());
-            *result = v.release();
-            return BMX_OK;
+            return agg_and_sub_finish(ctx, rc, v, st, offs, result, any);
         }
     }
-    uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub;
-    bmx_pipeline* praw = nullptr;
+    uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub; bmx_pipeline* praw = nullptr;
     if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw))) return rc;
     Owned<bmx_pipeline> p(praw);
     if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-    if (ncols && use_split(ctx, p.get(), ncols)) {
-        size_t lds = (size_t)SPLIT_WAVES * 8192;
-        auto fn = k_pipe_split<2, SPLIT_WAVES>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(fn, dim3(ncols), dim3(SPLIT_WAVES * 64), lds, ctx->stream,
-                               (const u64*)p->d_dmat, (const u32*)p->d_meta, (const u32*)(p->d_meta + 1), (const u32*)(p->d_meta + 2),
-                               p->col_stride, 1u, 0u, ncols, 1, (u64*)nullptr, 1, v->d_bits, v->d_desc, st);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) rc = fail_hip(e, "k_pipe_split", __LINE__);
-    } else if (ncols) rc = agg_and_sub_launch(ctx, p.get(), 0u, v.get(), st, 0u, 0xFFFFFFFFu);
-    if (!rc) rc = result_finish(ctx, v.get(), st, offs);
-    p.reset();
-    if (rc) return rc;
-    if (any) *any = vec_any_block(v.get());
-    *result = v.release();
-    return BMX_OK;
+    if (ncols) rc = agg_and_sub_launch(ctx, p.get(), 0u, v.get(), st, 0u, 0xFFFFFFFFu, true);
+    return agg_and_sub_finish(ctx, rc, v, st, offs, result, any);
 ABI_END }
 
 // combine_and_sub(pipe) with result vectors / counts / OR target (src/bmaggregator.h:1292-1449)

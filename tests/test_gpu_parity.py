@@ -577,14 +577,9 @@ def test_full_size_256way_and_count(ctx, port):
     assert t.count() == 0
 
 
-@pytest.mark.parametrize("tail_bits", [0, 5])
-def test_launch_shape_knobs_do_not_change_results(ctx, port, tail_bits):
-    """every tuning combination of the counts pipeline (slice size, batch size, NT, workgroup size, launch windows,
-    XCD swizzle) x every operand count 1..19 (pipeline tail handling) x AND / AND-SUB groups.
-    tail_bits 0: BIT / FULL / NULL blocks only -> the bit-only kernels k_pipe_counts_bits2<...> (the headline path);
-    tail_bits 5: the last block is a GAP block -> the general kernel k_pipe_counts (the shape knobs must be harmless)."""
+def _launch_shape_operands(ctx, port, tail_bits, nv=19):
+    """nv vectors of 13 blocks (+ tail_bits: a 14th, GAP, block) with FULL and NULL blocks among the bit-blocks -> (device, oracle)"""
     nbits = 13 * 65536 + tail_bits
-    nv = 19
     words = []
     for v in range(nv):
         w = port.gen_words(777, v, 20000, nbits) | port.gen_words(777, 0xFFFFFFFF, 9000, nbits)
@@ -593,8 +588,17 @@ def test_launch_shape_knobs_do_not_change_results(ctx, port, tail_bits):
         nw = (nbits + 31) // 32
         w[nw:] = 0; w[nw - 1] &= (1 << (nbits % 32)) - 1
         words.append(w)
-    gv = [bm.bit_import_u32(ctx, w, True) for w in words]
-    pv = [port.import_words(w, True, w.size * 32) for w in words]
+    return [bm.bit_import_u32(ctx, w, True) for w in words], [port.import_words(w, True, w.size * 32) for w in words]
+
+
+@pytest.mark.parametrize("tail_bits", [0, 5])
+def test_launch_shape_knobs_do_not_change_results(ctx, port, tail_bits):
+    """every tuning combination of the counts pipeline (slice size, batch size, NT, workgroup size, launch windows,
+    XCD swizzle) x every operand count 1..19 (pipeline tail handling) x AND / AND-SUB groups.
+    tail_bits 0: BIT / FULL / NULL blocks only -> the bit-only kernels k_pipe_counts_bits2<...> (the headline path);
+    tail_bits 5: the last block is a GAP block -> the general kernel k_pipe_counts (the shape knobs must be harmless)."""
+    nv = 19
+    gv, pv = _launch_shape_operands(ctx, port, tail_bits)
     has_gap = any(g.calc_stat()["gap_blocks"] for g in gv)
     assert has_gap == (tail_bits != 0)
     assert sum(g.calc_stat()["full_blocks"] for g in gv) >= 2 and sum(g.calc_stat()["null_blocks"] for g in gv) >= 2
@@ -664,6 +668,89 @@ def test_launch_shape_knobs_do_not_change_results(ctx, port, tail_bits):
         assert (t.to_words(14 * 2048) == e.to_words(14 * 2048)).all()
         o = agg.combine_or([gv[i] for i in a + s])
         assert (o.to_words(14 * 2048) == port.agg_or([pv[i] for i in a + s]).to_words(14 * 2048)).all()
+
+
+# what pipe.describe() printed for the cases of test_describe_is_the_launch_plan BEFORE the launch plan became one function
+# (taken from that library, not from the one under test), and the launches each line names.  One line differs on purpose:
+# the general kernel under pipe_window > 0 printed "k_pipe_counts<4> x 1 launch" while it launched four windows.
+_PLAN_TEXT = {
+    "general": ("k_pipe_counts<4> x 1 launch", 1),
+    "general_windows": ("k_pipe_counts<4> x 4 launches of <= 4 columns", 4),
+    "bits": ("k_pipe_counts_bits2<8,true,256,1> x 1 launch of <= 13 columns", 1),
+    "bits_windows": ("k_pipe_counts_bits2<8,true,256,1> x 4 launches of <= 4 columns", 4),
+    "bits_one_launch": ("k_pipe_counts_bits2<8,true,256,1> x 1 launch of <= 13 columns", 1),
+    "split": ("k_pipe_split<2,8> x 1 launch, 52 workgroups", 1),
+    "staged8": ("k_pipe_counts_staged<8> x 1 launch, 13 workgroups", 1),
+    "staged16": ("k_pipe_counts_staged<16> x 1 launch, 13 workgroups", 1),
+    "empty_range": ("k_pipe_counts_bits2<8,true,256,1> x 1 launch of <= 0 columns", 1),
+    "and_rows": ("k_agg_and_rows<COUNT,256,3> x 1 launch, 12 workgroups", 1),
+    "gapcount": ("k_pipe_counts_gapcount x 1 launch, 12 workgroups", 1),
+    "coll_whole": ("k_coll_apply<AND_COUNT,512> x 1 launch, 4 workgroups (packed collection of the operand set)", 1),
+    "coll_members": ("k_coll_members<AND_COUNT> x 1 launch, a wave per (column, group): 4 x 3 items (members of a packed collection)", 1),
+}
+_PLAN_KNOBS = (("pipe_window", 0), ("pipe_split", -1), ("pipe_staged", -1), ("pipe_slots", 16), ("and_rows", -1), ("gap_count", -1), ("coll_members", -1))
+
+
+def _plan_cases(ctx, port):
+    """every kernel family of a counts-only run, once: yields (name, pipeline, oracle groups, block range or None) with the
+    case's tuning keys in force.  Operands: the launch-shape vectors (13 bit-blocks; + a GAP block for the general kernel) and 16
+    GAP-only vectors of 4 blocks; a few arg-groups each."""
+    def make(gv, pv, groups, **knobs):
+        for k, x in _PLAN_KNOBS: ctx.set_tuning(k, knobs.get(k, x))
+        pipe = bm.aggregator.pipeline(ctx)
+        for a, s in groups:
+            ag = pipe.add()
+            for i in a: ag.add(gv[i], 0)
+            for i in s: ag.add(gv[i], 1)
+        pipe.complete()                                        # (the staged tables of a few-group pipeline exist only under pipe_staged 1)
+        return pipe, [([pv[i] for i in a], [pv[i] for i in s]) for a, s in groups]
+    few = [(list(range(5)), []), (list(range(8)), [8, 9]), ([0], [1]), (list(range(19)), [])]
+    bits, mixed = _launch_shape_operands(ctx, port, 0), _launch_shape_operands(ctx, port, 5)
+    assert not any(g.calc_stat()["gap_blocks"] for g in bits[0]) and any(g.calc_stat()["gap_blocks"] for g in mixed[0])
+    yield ("general",) + make(*mixed, few) + (None,)
+    yield ("general_windows",) + make(*mixed, few, pipe_window=4) + (None,)
+    yield ("bits",) + make(*bits, few) + (None,)
+    yield ("bits_windows",) + make(*bits, few, pipe_window=4) + (None,)
+    yield ("bits_one_launch",) + make(*bits, few, pipe_window=-1) + (None,)
+    yield ("split",) + make(*bits, few, pipe_split=1) + (None,)
+    yield ("staged8",) + make(*bits, few, pipe_staged=1, pipe_slots=8) + (None,)
+    yield ("staged16",) + make(*bits, few, pipe_staged=1, pipe_slots=16) + (None,)
+    yield ("empty_range",) + make(*bits, few) + ((3, 3),)
+    nbits = 4 * 65536
+    common = port.gen_words(777, 0xFFFFFFFF, 40, nbits)
+    words = [port.gen_words(777, 100 + v, (30, 120, 300)[v % 3], nbits) | common for v in range(16)]
+    gaps = [bm.bit_import_u32(ctx, w, True) for w in words], [port.import_words(w, True, w.size * 32) for w in words]
+    assert all(v.calc_stat()["bit_blocks"] == 0 and v.calc_stat()["gap_blocks"] for v in gaps[0]), "the case must stay GAP-only"
+    some = [(list(range(16)), []), (list(range(0, 16, 2)), []), (list(range(3, 12)), [])]
+    yield ("and_rows",) + make(*gaps, some, and_rows=1, pipe_split=0) + (None,)
+    yield ("gapcount",) + make(*gaps, some, gap_count=1, pipe_split=0) + (None,)
+    ctx.collection_prepare(gaps[0], bm.ROLE_AND)               # (goes with its vectors)
+    yield ("coll_whole",) + make(*gaps, some[:1], pipe_split=0) + (None,)
+    yield ("coll_members",) + make(*gaps, some, coll_members=1, pipe_split=0) + (None,)
+
+
+def test_describe_is_the_launch_plan(ctx, port):
+    """pipe.describe() / pipe.launches() are the plan the counts run launches (counts_plan in bmx.hip), not a second derivation
+    of it: for every kernel family the counts equal the oracle's, the text is what the library printed before the two were
+    joined (_PLAN_TEXT) and launches() is the number of launches that text names -- several where pipe_window cuts the 13 / 14
+    columns into windows of 4, the general kernel included."""
+    agg = bm.aggregator(ctx)
+    seen = []
+    try:
+        for name, pipe, groups, rng in _plan_cases(ctx, port):
+            if rng is None: got, exp = agg.combine_and_sub(pipe), port.pipeline_counts(groups)
+            else: got, exp = agg._run_pipeline(pipe, *rng), port.pipeline_counts(groups, *rng)
+            text, launches = _PLAN_TEXT[name]
+            d = pipe.describe(*rng) if rng else pipe.describe()       # (after the run: a collection serves a pipeline from its first run on)
+            n = pipe.launches(*rng) if rng else pipe.launches()
+            print(name, repr(d), n)
+            assert (got == exp).all(), (name, got, exp)
+            assert d == text, (name, d)
+            assert n == launches, (name, n)
+            seen.append(name)
+    finally:
+        for k, x in _PLAN_KNOBS: ctx.set_tuning(k, x)
+    assert seen == list(_PLAN_TEXT)
 
 
 @pytest.mark.parametrize("dq,nvec", [(13, 200), (60, 96), (65500, 70), (300, 33)])
