@@ -774,6 +774,23 @@ static Windows even_windows(u32 n, u32 cap)
     const u32 nwin = (cap && n) ? (n + cap - 1u) / cap : 1u;
     return {nwin, (n + nwin - 1u) / nwin};
 }
+// The launch of a streaming kernel over n >= 1 block columns: one machine-load of waves -- 256 CUs x wgs workgroups of `waves`
+// waves -- each wave owning a stretch of per_wave columns, the stretches cut evenly
+struct Stretch { u32 per_wave, grid; };
+static Stretch even_stretches(u64 n, u32 waves, int wgs)
+{
+    const u64 total = 256u * waves * (u32)std::max(wgs, 1);
+    const u64 per_wave = (n + total - 1u) / total;
+    return {(u32)per_wave, (u32)(((n + per_wave - 1u) / per_wave + waves - 1u) / waves)};
+}
+// what the streaming pairwise kernels take: bit-blocks only on both sides, equal length, at least 2,048 blocks
+static bool bits_only_pair(const bmx_vec* a, const bmx_vec* b)
+{
+    const uint32_t n = a->nblocks;
+    return n == b->nblocks && a->counts[BMX_BIT] == n && b->counts[BMX_BIT] == n && n >= 2048u;
+}
+// the GAP words a result can take over from this operand at most
+static uint64_t gap_bound_of(const bmx_vec* v) { return v->counts[BMX_GAP] ? v->gap_words : 0; }
 static void pipe_plan(const bmx_ctx* ctx, u64 nitems, u32 ngroups, u32& rows, u32& wg, u32& unroll, u32& window)
 {
     rows = (u32)ctx->pipe_rows;
@@ -1064,14 +1081,12 @@ int bmx_probe_stream_rw(bmx_ctx* ctx, uint64_t bytes, int sets, int wgs_per_cu, 
     void* buf = nullptr;
     HIPCHK(hipMalloc(&buf, (size_t)nblk * 8192 * 3 * sets));
     hipError_t e = hipMemsetAsync(buf, 0x5A, (size_t)nblk * 8192 * 3 * sets, ctx->stream);
-    const u32 waves = 4u, total = 256u * waves * (u32)wgs_per_cu;
-    const u32 per_wave = (u32)((nblk + total - 1u) / total);
-    const u32 grid = (u32)(((nblk + per_wave - 1u) / per_wave + waves - 1u) / waves);
+    const Stretch s = even_stretches(nblk, 4u, wgs_per_cu);
     for (int it = -2; it < iters && e == hipSuccess; ++it) {
         if (it == 0) e = hipEventRecord(ctx->ev0, ctx->stream);
         uint4* base = (uint4*)buf + (size_t)((it + 2) % sets) * nblk * 512u * 3u;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_rw<4>), dim3(grid), dim3(256), 0, ctx->stream, (const uint4*)base, (const uint4*)(base + nblk * 512u),
-                           base + 2u * nblk * 512u, (u32)nblk, per_wave);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_probe_rw<4>), dim3(s.grid), dim3(256), 0, ctx->stream, (const uint4*)base, (const uint4*)(base + nblk * 512u),
+                           base + 2u * nblk * 512u, (u32)nblk, s.per_wave);
     }
     if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
     if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
@@ -1999,12 +2014,10 @@ int bmx_i_count_async(bmx_ctx* ctx, const bmx_vec* a, int slot)
     int rc = set_dev(ctx); if (rc) return rc;
     if (!a->nblocks) { ctx->h_small[slot] = 0; return BMX_OK; }
     // the last workgroup folds the partial counts and writes the total straight into the pinned word the host reads
-    if (ctx->pair_stream != 0 && a->counts[BMX_BIT] == a->nblocks && a->nblocks >= 2048u) {     // bit-blocks only: the streaming form
-        const u32 total = 256u * 4u * (u32)std::max(ctx->pair_wgs, 1);
-        u32 per_wave = (a->nblocks + total - 1u) / total;
-        u32 grid = ((a->nblocks + per_wave - 1u) / per_wave + 3u) / 4u;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<4, true, 1>), dim3(grid), dim3(256), 0, ctx->stream, 0, a->d_desc, a->d_desc,
-                           a->nblocks, per_wave, FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + slot});
+    if (ctx->pair_stream != 0 && bits_only_pair(a, a)) {                                          // bit-blocks only: the streaming form
+        const Stretch s = even_stretches(a->nblocks, 4u, ctx->pair_wgs);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<4, true, 1>), dim3(s.grid), dim3(256), 0, ctx->stream, 0, a->d_desc, a->d_desc,
+                           a->nblocks, s.per_wave, FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + slot});
     } else
     hipLaunchKernelGGL(k_vec_count, dim3((a->nblocks + 3) / 4), dim3(256), 0, ctx->stream, a->d_desc, a->nblocks,
                        FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + slot});
@@ -2667,6 +2680,34 @@ static int result_begin(bmx_ctx* ctx, uint64_t nbits, uint32_t nblocks, Owned<bm
 // it holds, not 125 MB, and bmx_pipeline_run_results over G groups needs (sum of the live blocks) + ONE transient
 // slab.  A nearly full slab is kept as it is (no second pass over the blocks); its ordinals are kept in d_ord so
 // that bmx_vec_download moves only live blocks.
+static bool slab_sparse(uint32_t live, uint32_t nblocks) { return live && (uint64_t)live * 8u < (uint64_t)nblocks * 7u; }
+
+// ... of which `live` slots hold a bit-block.  The ordinals of the survivors are the layout scan's (st / offs, both) where the caller
+// ran it; without (both null) a compaction takes them from the descriptor table (k_ord_from_desc, into a temporary) and a kept slab
+// leaves them to the first download (ord_lazy).  Everything is enqueued, nothing waited for.
+static int bit_slab_settle(bmx_ctx* ctx, bmx_vec* v, uint32_t live, const BlockStat* st, const u32* offs)
+{
+    int rc;
+    const uint32_t nblocks = v->nblocks;
+    if (live == 0) {                          // nothing lives in the slab: give it back
+        dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0;
+    } else if (slab_sparse(live, nblocks)) {
+        DevBuf packed(ctx), ord(ctx);
+        if ((rc = dmalloc(ctx, &packed.p, (size_t)live * 8192)) || (!offs && (rc = dmalloc(ctx, &ord.p, (size_t)nblocks * 4)))) return rc;
+        if (!offs) hipLaunchKernelGGL(k_ord_from_desc, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)ord);
+        hipLaunchKernelGGL(k_compact_bits, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
+                           (const uint4*)v->d_bits, nblocks, st, offs ? offs : (const u32*)ord, (uint4*)packed, v->d_desc);
+        KCHK();
+        ord.reset(); dfree(ctx, v->d_bits);                              // (stream-ordered, see dfree)
+        v->d_bits = (uint4*)packed.release(); v->n_bit = live;
+    } else if (live < nblocks && !offs) v->ord_lazy = true;
+    else if (live < nblocks) {
+        if ((rc = dmalloc(ctx, (void**)&v->d_ord, (size_t)nblocks * 4))) return rc;
+        HIPCHK(hipMemcpyAsync(v->d_ord, offs, (size_t)nblocks * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return BMX_OK;
+}
+
 static int result_finish(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, bool gaps_done = false /* the kernel wrote its GAP blocks itself: only the bit slab is laid out */)
 {
     int rc;
@@ -2676,7 +2717,6 @@ static int result_finish(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, boo
     if ((rc = layout_read(ctx, st, nblocks, offs, &lay))) return rc;
     uint64_t gap_words = gaps_done ? 0 : lay.gap_words;
     memcpy(v->counts, lay.counts, sizeof(v->counts));
-    bool pending = false;
     if (gap_words) {
         size_t b_gaps = (size_t)gap_words * 2 + 64;      // + guard, see vec_alloc_device
         if ((rc = dmalloc(ctx, (void**)&v->d_gaps, b_gaps))) return rc;
@@ -2685,41 +2725,41 @@ static int result_finish(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, boo
         hipLaunchKernelGGL(k_emit_gaps, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
                            v->d_bits, nblocks, st, offs, v->d_gaps, v->d_desc);
         KCHK();
-        pending = true;
     }
-    uint32_t live = v->counts[BMX_BIT];
-    uint4* old_slab = nullptr;
-    if (live && (uint64_t)live * 8u < (uint64_t)nblocks * 7u) {
-        DevBuf packed(ctx);
-        if ((rc = dmalloc(ctx, &packed.p, (size_t)live * 8192))) return rc;
-        hipLaunchKernelGGL(k_compact_bits, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                           (const uint4*)v->d_bits, nblocks, (const BlockStat*)st, (const u32*)offs, (uint4*)packed, v->d_desc);
-        KCHK();
-        old_slab = v->d_bits; v->d_bits = (uint4*)packed.release(); v->n_bit = live;
-        pending = true;
-    } else if (live && live < nblocks) {
-        if ((rc = dmalloc(ctx, (void**)&v->d_ord, (size_t)nblocks * 4))) return rc;
-        HIPCHK(hipMemcpyAsync(v->d_ord, offs, (size_t)nblocks * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        pending = true;
-    }
-    // Nothing enqueued above is waited for: everything it reads (st / offs in the context's scratch, the old slab) is next
-    // touched by work that is enqueued BEHIND it on the same stream -- the scratch by the next operation (ensure() synchronises
-    // before it ever re-allocates), a pooled block by whoever is handed it next (hipFree, when the pool overflows, synchronises
-    // the device) -- and the host needs nothing more from the device here: the kinds came with the synchronise above.
-    (void)pending;
-    if (old_slab) dfree(ctx, old_slab);
-    if (live == 0) {                          // nothing lives in the slab: give it back
-        dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0;
-    }
-    return BMX_OK;
+    // Nothing enqueued above or by bit_slab_settle is waited for: everything it reads (st / offs in the context's scratch, the old
+    // slab) is next touched by work that is enqueued BEHIND it on the same stream -- the scratch by the next operation (ensure()
+    // synchronises before it ever re-allocates), a pooled block by whoever is handed it next (hipFree, when the pool overflows,
+    // synchronises the device) -- and the host needs nothing more from the device here: the kinds came with the synchronise above.
+    return bit_slab_settle(ctx, v, v->counts[BMX_BIT], st, offs);
+}
+
+// The in-kernel fold of a result's block kinds, as the host finds it in its eight-word pinned slot: four kind counts, then -- from
+// a kernel that laid its GAP results out -- the cursor, words | GAP blocks << 40.  fold_read also holds it against the vector:
+// BMX_ERR_DEVICE when the kinds do not add up to nblocks or the cursor disagrees with them or passed the slab's bound (the caller
+// words the message).
+struct Fold { uint32_t counts[4]; uint64_t used, ncand; };
+static Fold fold_decode(const u64* slot)
+{
+    Fold f;
+    for (int k = 0; k < 4; ++k) f.counts[k] = (uint32_t)slot[k];
+    f.used = slot[4] & 0xFFFFFFFFFFull; f.ncand = slot[4] >> 40;
+    return f;
+}
+static int fold_read(const u64* slot, uint32_t nblocks, uint64_t bound, Fold* f)
+{
+    *f = fold_decode(slot);
+    const bool ok = (uint64_t)f->counts[0] + f->counts[1] + f->counts[2] + f->counts[3] == nblocks && f->ncand == f->counts[BMX_GAP] &&
+                    (f->used == 0) == (f->ncand == 0) && f->used <= bound;
+    return ok ? BMX_OK : BMX_ERR_DEVICE;
 }
 
 // The tail of a call whose kernel folded the kinds of its result into h_small[2..5] (the stream has been synchronised): when
 // every block came out a bit-block there is nothing for the layout scan to lay out, else result_finish
 static int result_finish_folded(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs)
 {
-    if (ctx->h_small[2 + BMX_GAP] != 0 || ctx->h_small[2 + BMX_BIT] != v->nblocks) return result_finish(ctx, v, st, offs);
-    for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)ctx->h_small[2 + k];
+    const Fold f = fold_decode(ctx->h_small + 2);            // (no cursor behind these kinds: word 4 is not this kernel's)
+    if (f.counts[BMX_GAP] != 0 || f.counts[BMX_BIT] != v->nblocks) return result_finish(ctx, v, st, offs);
+    memcpy(v->counts, f.counts, sizeof(v->counts));
     return BMX_OK;
 }
 
@@ -2759,17 +2799,68 @@ static int vec_clone(bmx_ctx* ctx, const bmx_vec* a, bmx_vec** out)
 
 } // extern "C"
 
-// k_op2_loop's launch: op2_loop N > 0 = N workgroups of 4 waves per CU, -1 = 4 of them.  (Measured and dropped, profiles/r05_pair: ONE
-// 16-wave workgroup per CU when GAP results can come out, so that the conversions of its tail spread over 16 waves -- the tail
-// then starts when the slowest of 16 waves has left the column loop: AND 0.078 -> 0.082 ms, SUB 0.085 -> 0.086 ms.)
-static void op2_loop_launch(bmx_ctx* ctx, int op, const bmx_vec* va, const bmx_vec* vb, u32 nblocks, int opt_compress, bmx_vec* v, BlockStat* st,
-                            FoldOut fo, u32* offs, u16* gap_slab)
+// ---- one materialised pairwise operation: which kernel and what it folds (op2_plan), its launch (op2_launch) ----
+// bmx_op2 and bmx_op2_dev share both; where the two entries differ, the difference is an input of the plan.
+enum Op2Family { OP2_STREAM, OP2_LOOP, OP2_COLUMN };
+struct Op2Plan {
+    Op2Family family;
+    bool lays_out;       // the kernel lays its GAP results out itself: bump cursor, offs[], a GAP slab sized at the operands' bound
+    bool fold_kinds;     // the kernel folds the kind counts of its result into the entry's pinned slot
+    bool fold_count;     // ... and the popcount of its result (d_slots2 -> h_small[8])
+};
+// No HIP call.  `async`: bmx_op2_dev, which cannot wait for a layout scan; `resolved`: both operands are vectors whose kind counts
+// the host knows (bmx_op2: always); `gap_in`: an operand holds GAP blocks (an unresolved one: may hold -- its GAP bound is non-zero)
+static Op2Plan op2_plan(const bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, uint32_t nblocks, int opt_compress,
+                        bool async, bool resolved, bool gap_in)
 {
-    const u32 wgs = (u32)(ctx->op2_loop > 0 ? ctx->op2_loop : 4);        // workgroups per CU = waves per SIMD
-    const u32 grid = std::min<u32>((nblocks + 3u) / 4u, 256u * wgs);
-    auto fn = (ctx->op2_nt & 1) ? k_op2_loop<4, true> : k_op2_loop<4, false>;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, op, va->d_desc, va->nblocks, vb->d_desc, vb->nblocks, nblocks, opt_compress,
-                       v->d_bits, v->d_desc, st, fo, offs, ctx->d_cursor, gap_slab);
+    // no GAP block can come out (neither operand holds one, no re-compression): the kernel folds the kind counts itself
+    // and the layout scan is skipped -- one launch, one synchronise, done -- unless result blocks vanished (then the scan /
+    // compaction path decides what to do with the slab)
+    const bool no_gap = !opt_compress && !gap_in;
+    // bit-blocks only on both sides: the streaming form (one machine-load of waves, each owning a stretch of columns).  The
+    // kinds of an unresolved operand are not known yet: the asynchronous entry streams resolved vectors only.
+    if (resolved && no_gap && ctx->pair_stream != 0 && bits_only_pair(a, b)) return {OP2_STREAM, false, true, false};
+    // Without re-compression the loop kernel also lays its GAP candidates out (a bump cursor instead of the layout scan), converts
+    // them in its tail into a slab sized at the operands' bound, and folds the kinds: nothing is left after the one
+    // synchronise -- unless the bit slab turns out sparse enough to be compacted, which takes the scan path as before.
+    // (The 16-bit kind counters of a fold slot hold 64 x 65,535 blocks; bmx_op2_dev refuses longer operands.)
+    const bool can_lay_out = !opt_compress && gap_in && nblocks <= 2000000u;
+    // any block kinds, long vectors: the persistent form (one memory round trip per column, GAP blocks decoded from registers).
+    // The asynchronous entry takes it whatever the length and whatever op2_loop says when a GAP block can come out: its result must
+    // be complete on the stream, and only this kernel lays out.
+    // The kinds are folded whatever the operands hold: when every block came out as a bit-block (OR / XOR of two 1 % vectors:
+    // their GAP x GAP results pass the 1,276-run limit) there is nothing for the layout scan to lay out.  (With re-compression
+    // the synchronous AND / SUB go straight to the layout scan, no extra synchronise; the asynchronous entry has only the fold.)
+    if ((ctx->op2_loop != 0 && nblocks >= 2048u) || (async && can_lay_out))
+        return {OP2_LOOP, can_lay_out, async || can_lay_out || no_gap || op == BMX_OR || op == BMX_XOR, false};
+    // short vectors: a wave per column; for the synchronous entry the kernel also folds the popcount of its result (bvector::bit_and +
+    // count(), the plumbing case of BASELINE configs[0], is then ONE launch and one synchronise: bmx_count finds the count with the vector)
+    return {OP2_COLUMN, false, async || no_gap, !async};
+}
+
+// The launch of what the plan names, the only one of k_op2_loop, k_op2_stream and k_op2 (named in this order: the code object holds
+// them so).  kinds_out: the entry's pinned slot for the fold of the kinds; a kernel that lays out takes offs[] and v's GAP slab.
+static void op2_launch(bmx_ctx* ctx, const Op2Plan& pl, int op, const bmx_vec* a, const bmx_vec* b, uint32_t nblocks, int opt_compress,
+                       bmx_vec* v, BlockStat* st, u32* offs, u64* kinds_out)
+{
+    const FoldOut none{nullptr, nullptr, nullptr}, kinds = pl.fold_kinds ? FoldOut{ctx->d_slots, ctx->d_done, kinds_out} : none;
+    if (pl.family == OP2_LOOP) {
+        // op2_loop N > 0 = N workgroups of 4 waves per CU, -1 (and 0, from the asynchronous entry) = 4 of them.  (Measured and dropped,
+        // profiles/r05_pair: ONE 16-wave workgroup per CU when GAP results can come out, so that the conversions of its tail spread over
+        // 16 waves -- the tail then starts when the slowest of 16 waves has left the column loop: AND 0.078 -> 0.082 ms, SUB 0.085 -> 0.086 ms.)
+        const u32 wgs = (u32)(ctx->op2_loop > 0 ? ctx->op2_loop : 4);        // workgroups per CU = waves per SIMD
+        const u32 grid = std::min<u32>((nblocks + 3u) / 4u, 256u * wgs);
+        auto fn = (ctx->op2_nt & 1) ? k_op2_loop<4, true> : k_op2_loop<4, false>;
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, op, a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, opt_compress,
+                           v->d_bits, v->d_desc, st, kinds, pl.lays_out ? offs : (u32*)nullptr, ctx->d_cursor, pl.lays_out ? v->d_gaps : (u16*)nullptr);
+    } else if (pl.family == OP2_STREAM) {
+        const Stretch s = even_stretches(nblocks, 4u, ctx->op2_wgs);
+        auto fn = ctx->op2_nt == 3 ? k_op2_stream<4, true, true> : ctx->op2_nt == 2 ? k_op2_stream<4, false, true>
+                : ctx->op2_nt == 1 ? k_op2_stream<4, true, false> : k_op2_stream<4, false, false>;
+        hipLaunchKernelGGL(fn, dim3(s.grid), dim3(256), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, s.per_wave, v->d_bits, v->d_desc, st, kinds);
+    } else
+        hipLaunchKernelGGL(k_op2, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, op, a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, opt_compress,
+                           v->d_bits, v->d_desc, st, kinds, pl.fold_count ? FoldOut{ctx->d_slots2, ctx->d_done2, ctx->h_small + 8} : none);
 }
 
 // A GAP slab allocated at the operands' bound (the words a pairwise result can hold at most: a copied GAP block, a GAP x GAP
@@ -2799,21 +2890,26 @@ static int gap_slab_trim(bmx_ctx* ctx, bmx_vec* v, uint64_t bound, uint64_t used
 // and with it a GAP slab whose slack stays under a quarter of the bytes the vector keeps in bit-blocks anyway.
 static int op2_finish_laid_out(bmx_ctx* ctx, bmx_vec* v, BlockStat* st, u32* offs, uint64_t bound)
 {
-    const uint32_t nblocks = v->nblocks;
-    uint32_t counts[4];
-    for (int k = 0; k < 4; ++k) counts[k] = (uint32_t)ctx->h_small[2 + k];
-    const uint64_t used = ctx->h_small[6] & 0xFFFFFFFFFFull, ncand = ctx->h_small[6] >> 40;      // the cursor: words | GAP blocks << 40
-    if ((uint64_t)counts[0] + counts[1] + counts[2] + counts[3] != nblocks || ncand != counts[BMX_GAP] || (used == 0) != (ncand == 0) || used > bound) {
-        g_last_error = "bmx_op2: inconsistent fold of the result block kinds"; return BMX_ERR_DEVICE;
-    }
-    const uint32_t live = counts[BMX_BIT];
-    const bool sparse = live && live < nblocks && (uint64_t)live * 8u < (uint64_t)nblocks * 7u;
-    int rc = gap_slab_trim(ctx, v, bound, used, sparse ? 0 : (size_t)live * 2048u);
+    Fold f;
+    if (fold_read(ctx->h_small + 2, v->nblocks, bound, &f)) { g_last_error = "bmx_op2: inconsistent fold of the result block kinds"; return BMX_ERR_DEVICE; }
+    const uint32_t live = f.counts[BMX_BIT];
+    const bool sparse = slab_sparse(live, v->nblocks);
+    int rc = gap_slab_trim(ctx, v, bound, f.used, sparse ? 0 : (size_t)live * 2048u);
     if (rc) return rc;
     if (sparse) return result_finish(ctx, v, st, offs, true);
-    memcpy(v->counts, counts, sizeof(counts));
-    if (live == 0) { dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0; }
-    else if (live < nblocks) v->ord_lazy = true;
+    memcpy(v->counts, f.counts, sizeof(f.counts));
+    return bit_slab_settle(ctx, v, live, nullptr, nullptr);
+}
+
+// One unresolved result more: a free slot of h_pend and the event its producer records (pending_release gives both back)
+static int pend_claim(bmx_ctx* ctx, bmx_pending* p)
+{
+    int slot = -1;
+    for (int i = 0; i < PEND_SLOTS; ++i) if (!(ctx->pend_used[i >> 6] >> (i & 63) & 1ull)) { slot = i; break; }
+    if (slot < 0) { g_last_error = "bmx_op2_dev: 1,024 unresolved results are outstanding (bmx_pending_wait / bmx_pending_free them)"; return BMX_ERR_RANGE; }
+    hipError_t e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
+    if (e != hipSuccess) return fail_hip(e, "hipEventCreate", __LINE__);
+    p->slot = slot; ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
     return BMX_OK;
 }
 
@@ -2833,62 +2929,18 @@ int bmx_op2(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_vec* b, int opt_co
     }
     Owned<bmx_vec> v; BlockStat* st; u32* offs;
     if ((rc = result_begin(ctx, nbits, nblocks, &v, &st, &offs))) return rc;
-    // no GAP block can come out (neither operand holds one, no re-compression): the kernel folds the kind counts itself
-    // and the layout scan is skipped -- k_op2, one synchronise, done -- unless result blocks vanished (then the scan /
-    // compaction path below decides what to do with the slab)
-    bool no_gap = !opt_compress && a->counts[BMX_GAP] == 0 && b->counts[BMX_GAP] == 0, folded = false, emit = false, counted = false;
-    uint64_t gap_bound = 0;
-    if (nblocks) {
-        // bit-blocks only on both sides: the streaming form (one machine-load of waves, each owning a stretch of columns)
-        const bool stream = no_gap && ctx->pair_stream != 0 && a->nblocks == b->nblocks && a->counts[BMX_BIT] == nblocks &&
-                            b->counts[BMX_BIT] == nblocks && nblocks >= 2048u;
-        if (stream) {
-            const u32 waves = 4u, total = 256u * waves * (u32)std::max(ctx->op2_wgs, 1);
-            const u32 per_wave = (nblocks + total - 1u) / total;
-            const u32 grid = ((nblocks + per_wave - 1u) / per_wave + waves - 1u) / waves;
-            auto fn = ctx->op2_nt == 3 ? k_op2_stream<4, true, true> : ctx->op2_nt == 2 ? k_op2_stream<4, false, true>
-                    : ctx->op2_nt == 1 ? k_op2_stream<4, true, false> : k_op2_stream<4, false, false>;
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, per_wave,
-                               v->d_bits, v->d_desc, st, FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2});
-        } else if (ctx->op2_loop != 0 && nblocks >= 2048u) {
-            // any block kinds, long vectors: the persistent form (one memory round trip per column, GAP blocks decoded from registers)
-            // Without re-compression the kernel also lays its GAP candidates out (a bump cursor instead of the layout scan), converts
-            // them in its tail into a slab sized at the operands' bound, and folds the kinds: nothing is left after the one
-            // synchronise -- unless the bit slab turns out sparse enough to be compacted, which takes the scan path as before.
-            // (The 16-bit kind counters of a fold slot hold 64 x 65,535 blocks.)
-            emit = !opt_compress && !no_gap && nblocks <= 2000000u;
-            if (emit) {
-                gap_bound = (a->counts[BMX_GAP] ? a->gap_words : 0) + (b->counts[BMX_GAP] ? b->gap_words : 0) + 8u;
-                if ((rc = dmalloc(ctx, (void**)&v->d_gaps, (size_t)gap_bound * 2 + 64))) return rc;
-            }
-            // the kinds are folded whatever the operands hold: when every block came out as a bit-block (OR / XOR of two 1 % vectors:
-            // their GAP x GAP results pass the 1,276-run limit) there is nothing for the layout scan to lay out
-            op2_loop_launch(ctx, op, a, b, nblocks, opt_compress, v.get(), st,
-                            (emit || no_gap || op == BMX_OR || op == BMX_XOR) ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr},
-                            emit ? offs : (u32*)nullptr, emit ? v->d_gaps : (u16*)nullptr);
-            folded = emit || op == BMX_OR || op == BMX_XOR;                 // (with re-compression AND / SUB go straight to the layout scan, no extra synchronise)
-        } else {
-        // short vectors: a wave per column; the kernel also folds the popcount of its result (bvector::bit_and + count(), the
-        // plumbing case of BASELINE configs[0], is then ONE launch and one synchronise: bmx_count finds the count with the vector)
-        hipLaunchKernelGGL(k_op2, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, op,
-                           a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, opt_compress,
-                           v->d_bits, v->d_desc, st,
-                           no_gap ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr},
-                           FoldOut{ctx->d_slots2, ctx->d_done2, ctx->h_small + 8});
-        counted = true;
-        }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess && (no_gap || folded)) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail_hip(e, "k_op2", __LINE__);
-        if (emit) {
-            if ((rc = op2_finish_laid_out(ctx, v.get(), st, offs, gap_bound))) return rc;
-            *result = v.release();
-            return BMX_OK;
-        }
-    }
+    if (!nblocks) { *result = v.release(); return BMX_OK; }
+    const Op2Plan pl = op2_plan(ctx, op, a, b, nblocks, opt_compress, false, true, a->counts[BMX_GAP] != 0 || b->counts[BMX_GAP] != 0);
+    const uint64_t gap_bound = gap_bound_of(a) + gap_bound_of(b) + 8u;
+    if (pl.lays_out && (rc = dmalloc(ctx, (void**)&v->d_gaps, (size_t)gap_bound * 2 + 64))) return rc;
+    op2_launch(ctx, pl, op, a, b, nblocks, opt_compress, v.get(), st, offs, ctx->h_small + 2);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && pl.fold_kinds) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail_hip(e, "k_op2", __LINE__);
     // (result_finish synchronises: the folded count has arrived either way)
-    if ((rc = nblocks && (no_gap || folded) ? result_finish_folded(ctx, v.get(), st, offs) : result_finish(ctx, v.get(), st, offs))) return rc;
-    if (counted) { v->count = ctx->h_small[8]; v->count_valid = true; }
+    if ((rc = pl.lays_out ? op2_finish_laid_out(ctx, v.get(), st, offs, gap_bound)
+            : pl.fold_kinds ? result_finish_folded(ctx, v.get(), st, offs) : result_finish(ctx, v.get(), st, offs))) return rc;
+    if (pl.fold_count) { v->count = ctx->h_small[8]; v->count_valid = true; }
     *result = v.release();
     return BMX_OK;
 ABI_END }
@@ -2920,94 +2972,67 @@ int bmx_op2_dev(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_pending* pa, c
     ARGCHK(ctx && out && op >= BMX_AND && op <= BMX_SUB && ((a != nullptr) != (pa != nullptr)) && ((b != nullptr) != (pb != nullptr)));
     *out = nullptr;
     ARGCHK((!a || a->ctx == ctx) && (!b || b->ctx == ctx) && (!pa || pa->ctx == ctx) && (!pb || pb->ctx == ctx));
-    // operands that may hold GAP blocks: the result may hold GAP blocks too -- at most the operands' GAP words together
-    // (a copied GAP block, a GAP x GAP result of at most len(a) + len(b) runs) -- so its GAP slab is allocated at that bound
-    // and the kernel converts its GAP candidates into it before it ends: the descriptors are complete on the stream and the
-    // result can be an operand at once; bmx_pending_wait trims the slab
-    const uint64_t gap_bound = (a ? (a->counts[BMX_GAP] ? a->gap_words : 0) : pa->gap_bound) + (b ? (b->counts[BMX_GAP] ? b->gap_words : 0) : pb->gap_bound);
+    // operands that may hold GAP blocks: the result may hold GAP blocks too, at most the operands' GAP words together (see gap_slab_trim).
+    // Its GAP slab is allocated at that bound and the kernel converts its GAP candidates into it before it ends: the descriptors are
+    // complete on the stream and the result can be an operand at once; bmx_pending_wait trims the slab
+    const uint64_t gap_bound = (a ? gap_bound_of(a) : pa->gap_bound) + (b ? gap_bound_of(b) : pb->gap_bound);
     int rc = set_dev(ctx); if (rc) return rc;
     const bmx_vec* va = a ? a : pa->v; const bmx_vec* vb = b ? b : pb->v;
     const uint32_t nblocks = std::max(va->nblocks, vb->nblocks);
     const uint64_t nbits = std::max(va->nbits, vb->nbits);
     if (nblocks > 2000000u) { g_last_error = "bmx_op2_dev: more than 2,000,000 blocks (the in-kernel fold of the kind counts holds 64 x 65,535): use bmx_op2"; return BMX_ERR_RANGE; }
-    int slot = -1;
-    for (int i = 0; i < PEND_SLOTS; ++i) if (!(ctx->pend_used[i >> 6] >> (i & 63) & 1ull)) { slot = i; break; }
-    if (slot < 0) { g_last_error = "bmx_op2_dev: 1,024 unresolved results are outstanding (bmx_pending_wait / bmx_pending_free them)"; return BMX_ERR_RANGE; }
     Owned<bmx_pending> p(new bmx_pending());
     p->ctx = ctx;
-    if (((a && a == b) || (pa && pa == pb)) && (op == BMX_AND || op == BMX_OR)) {
+    if ((rc = pend_claim(ctx, p.get()))) return rc;
+    const bool same = (a && a == b) || (pa && pa == pb);
+    if (same && (op == BMX_AND || op == BMX_OR)) {
         // aliasing as the reference handles it up front (src/bm.h:6191-6195, 5984-5988): x & x, x | x are block-for-block copies,
         // nothing is re-classified.  An unresolved operand is waited for here (its kind counts are the copy's).
         const bmx_vec* src = a ? a : pa->v;
-        uint32_t cnt[4]; uint64_t used = src->gap_words;
-        memcpy(cnt, src->counts, sizeof(cnt));
+        Fold f{{}, src->gap_words, 0};
+        memcpy(f.counts, src->counts, sizeof(f.counts));
         if (pa && !pa->resolved) {
             hipError_t ew = hipEventSynchronize(pa->ev);
             if (ew != hipSuccess) return fail_hip(ew, "bmx_op2_dev (alias)", __LINE__);
-            const u64* ps = ctx->h_pend + (size_t)pa->slot * 8;
-            for (int k = 0; k < 4; ++k) cnt[k] = (uint32_t)ps[k];
-            used = ps[4] & 0xFFFFFFFFFFull;
+            f = fold_decode(ctx->h_pend + (size_t)pa->slot * 8);
         }
         bmx_vec* c = nullptr;
         if ((rc = vec_clone(ctx, src, &c))) return rc;
         p->v = c;
-        memcpy(c->counts, cnt, sizeof(cnt));
+        memcpy(c->counts, f.counts, sizeof(f.counts));
         c->count_valid = false;
-        if (c->d_gaps) c->gap_words = used;                                  // (an unresolved source: its slab is sized at the bound, its data end at `used`)
-        if (c->d_bits && c->n_bit == c->nblocks && cnt[BMX_BIT] < c->nblocks && !c->d_ord) c->ord_lazy = true;
-        hipError_t ee = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
-        if (ee == hipSuccess) ee = hipEventRecord(p->ev, ctx->stream);
+        if (c->d_gaps) c->gap_words = f.used;                                // (an unresolved source: its slab is sized at the bound, its data end at `used`)
+        if (c->d_bits && c->n_bit == c->nblocks && f.counts[BMX_BIT] < c->nblocks && !c->d_ord) c->ord_lazy = true;
+        hipError_t ee = hipEventRecord(p->ev, ctx->stream);
         if (ee != hipSuccess) return fail_hip(ee, "bmx_op2_dev (alias)", __LINE__);
         p->resolved = true; p->gap_bound = c->d_gaps ? c->gap_words : 0;
-        p->slot = slot; ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
         *out = p.release();
         return BMX_OK;
     }
     Owned<bmx_vec> res; BlockStat* st; u32* offs;
     if ((rc = result_begin(ctx, nbits, nblocks, &res, &st, &offs))) return rc;
     bmx_vec* v = p->v = res.release();
-    u16* gap_slab = nullptr;
-    if (gap_bound && nblocks) {
+    const Op2Plan pl = op2_plan(ctx, op, va, vb, nblocks, 0, true, a && b, gap_bound != 0);
+    if (pl.lays_out && nblocks) {
         // this result's own st[] / offs[] / candidate list (the context's scratch is the next operation's) and its GAP slab
         const uint64_t bound = gap_bound + 8u;
         if ((rc = dmalloc(ctx, &p->scratch, (size_t)nblocks * (sizeof(BlockStat) + 8) + 64)) || (rc = dmalloc(ctx, (void**)&v->d_gaps, (size_t)bound * 2 + 64))) return rc;
-        gap_slab = v->d_gaps;
         st = (BlockStat*)p->scratch; offs = (u32*)((char*)p->scratch + (size_t)nblocks * sizeof(BlockStat));
         v->gap_words = bound; v->bytes += (size_t)bound * 2 + 64;
         p->gap_bound = bound;
     }
-    u64* hs = ctx->h_pend + (size_t)slot * 8;
-    for (int k = 0; k < 8; ++k) hs[k] = 0;
-    hipError_t e = hipEventCreateWithFlags(&p->ev, hipEventDisableTiming);
-    if (e != hipSuccess) return fail_hip(e, "hipEventCreate", __LINE__);
-    const FoldOut fo{ctx->d_slots, ctx->d_done, hs};
-    const bool same = (a && b && a == b) || (pa && pb && pa == pb);
-    if (!nblocks) hs[BMX_NULL] = 0;
-    else if (same && (op == BMX_XOR || op == BMX_SUB)) {                    // x ^ x, x - x: empty (src/bm.h:6081, 6412)
+    u64* hs = ctx->h_pend + (size_t)p->slot * 8;
+    for (int k = 0; k < 8; ++k) hs[k] = 0;                                  // (all there is to the fold of an empty result)
+    hipError_t e = hipSuccess;
+    if (nblocks && same && (op == BMX_XOR || op == BMX_SUB)) {              // x ^ x, x - x: empty (src/bm.h:6081, 6412)
         e = hipMemsetAsync(v->d_desc, 0, (size_t)nblocks * 8, ctx->stream);
         hs[BMX_NULL] = nblocks;
-    } else {
-        const bool stream = a && b && ctx->pair_stream != 0 && a->nblocks == b->nblocks && a->counts[BMX_BIT] == nblocks &&
-                            b->counts[BMX_BIT] == nblocks && nblocks >= 2048u;
-        if (gap_slab) {
-            op2_loop_launch(ctx, op, va, vb, nblocks, 0, v, st, fo, offs, gap_slab);
-        } else if (stream) {
-            const u32 waves = 4u, total = 256u * waves * (u32)std::max(ctx->op2_wgs, 1);
-            const u32 per_wave = (nblocks + total - 1u) / total;
-            const u32 grid = ((nblocks + per_wave - 1u) / per_wave + waves - 1u) / waves;
-            auto fn = ctx->op2_nt == 3 ? k_op2_stream<4, true, true> : ctx->op2_nt == 2 ? k_op2_stream<4, false, true>
-                    : ctx->op2_nt == 1 ? k_op2_stream<4, true, false> : k_op2_stream<4, false, false>;
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, op, va->d_desc, vb->d_desc, nblocks, per_wave, v->d_bits, v->d_desc, st, fo);
-        } else if (ctx->op2_loop != 0 && nblocks >= 2048u) {
-            op2_loop_launch(ctx, op, va, vb, nblocks, 0, v, st, fo, nullptr, nullptr);
-        } else
-            hipLaunchKernelGGL(k_op2, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, op, va->d_desc, va->nblocks, vb->d_desc, vb->nblocks, nblocks, 0,
-                               v->d_bits, v->d_desc, st, fo, FoldOut{nullptr, nullptr, nullptr});
+    } else if (nblocks) {
+        op2_launch(ctx, pl, op, va, vb, nblocks, 0, v, st, offs, hs);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(p->ev, ctx->stream);
     if (e != hipSuccess) return fail_hip(e, "bmx_op2_dev", __LINE__);
-    p->slot = slot; ctx->pend_used[slot >> 6] |= 1ull << (slot & 63);
     *out = p.release();
     return BMX_OK;
 ABI_END }
@@ -3025,32 +3050,18 @@ int bmx_pending_wait(bmx_ctx* ctx, bmx_pending* p, bmx_vec** out)
         *out = v.release();
         return BMX_OK;
     }
-    const u64* hs = ctx->h_pend + (size_t)p->slot * 8;
-    const uint32_t nblocks = v->nblocks;
-    for (int k = 0; k < 4; ++k) v->counts[k] = (uint32_t)hs[k];
-    const uint64_t used = hs[4] & 0xFFFFFFFFFFull, ncand = hs[4] >> 40, bound = p->gap_bound;
-    const bool ok = (uint64_t)v->counts[0] + v->counts[1] + v->counts[2] + v->counts[3] == nblocks && ncand == v->counts[BMX_GAP] &&
-                    used <= bound && (used == 0) == (ncand == 0);
+    const uint64_t bound = p->gap_bound;
+    Fold f;
+    const int bad = fold_read(ctx->h_pend + (size_t)p->slot * 8, v->nblocks, bound, &f);
     (void)pending_release(p);                                         // (its scratch: the kernel that wrote it ran before the event)
-    if (!ok) { v.reset(); g_last_error = "bmx_pending_wait: inconsistent fold of the result block kinds"; return BMX_ERR_DEVICE; }
+    if (bad) { v.reset(); g_last_error = "bmx_pending_wait: inconsistent fold of the result block kinds"; return bad; }
+    memcpy(v->counts, f.counts, sizeof(f.counts));
     if (bound) {
         v->bytes -= std::min<size_t>(v->bytes, (size_t)bound * 2 + 64);
-        if ((rc = gap_slab_trim(ctx, v.get(), bound, used, 0))) return rc;
+        if ((rc = gap_slab_trim(ctx, v.get(), bound, f.used, 0))) return rc;
     }
-    // the slab, as result_finish treats it: nothing alive -> back to the pool; sparse -> the survivors into a right-sized slab
-    // (ordinals from the descriptor table; enqueued, not waited for); nearly full -> kept, ordinals at the first download
-    const uint32_t live = v->counts[BMX_BIT];
-    if (live == 0) { dfree(ctx, v->d_bits); v->d_bits = nullptr; v->n_bit = 0; }
-    else if ((uint64_t)live * 8u < (uint64_t)nblocks * 7u) {
-        DevBuf packed(ctx), ord(ctx);
-        if ((rc = dmalloc(ctx, &packed.p, (size_t)live * 8192)) || (rc = dmalloc(ctx, &ord.p, (size_t)nblocks * 4))) return rc;
-        hipLaunchKernelGGL(k_ord_from_desc, dim3(1), dim3(1024), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)ord);
-        hipLaunchKernelGGL(k_compact_bits, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                           (const uint4*)v->d_bits, nblocks, (const BlockStat*)nullptr, (const u32*)ord, (uint4*)packed, v->d_desc);
-        if (hipError_t e = hipGetLastError()) return fail_hip(e, "bmx_pending_wait (compaction)", __LINE__);
-        ord.reset(); dfree(ctx, v->d_bits);                              // (stream-ordered, see dfree)
-        v->d_bits = (uint4*)packed.release(); v->n_bit = live;
-    } else if (live < nblocks) v->ord_lazy = true;
+    // the slab, as result_finish treats it; no layout scan ran: a compaction takes the ordinals from the descriptor table
+    if ((rc = bit_slab_settle(ctx, v.get(), f.counts[BMX_BIT], nullptr, nullptr))) return rc;
     *out = v.release();
     return BMX_OK;
 ABI_END }
@@ -3067,37 +3078,27 @@ static int count_op2_launch(bmx_ctx* ctx, int op, const bmx_vec* a, const bmx_ve
         if (out_is_host) *out = 0; else HIPCHK(hipMemsetAsync(out, 0, 8, ctx->stream));
         return BMX_OK;
     }
-    // bit-blocks only on both sides, same length: the streaming form (a wave per stretch of columns, one workgroup per CU)
-    if (ctx->pair_stream != 0 && a->nblocks == b->nblocks && a->counts[BMX_BIT] == nblocks && b->counts[BMX_BIT] == nblocks &&
-        nblocks >= 2048u) {
+    const FoldOut fo{ctx->d_slots, ctx->d_done, out};
+    if (ctx->pair_stream != 0 && bits_only_pair(a, b)) {
+        // bit-blocks only on both sides, same length: the streaming form (a wave per stretch of columns, one workgroup per CU)
         const u32 waves = ctx->pair_stream > 0 ? (u32)ctx->pair_stream : 4u;      // per workgroup
-        const u32 total = 256u * waves * (u32)std::max(ctx->pair_wgs, 1);        // waves of the launch
-        u32 per_wave = (nblocks + total - 1u) / total;
-        u32 grid = ((nblocks + per_wave - 1u) / per_wave + waves - 1u) / waves;
-        FoldOut fo{ctx->d_slots, ctx->d_done, out};
-        if (waves == 2u) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<2, true>), dim3(grid), dim3(128), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, per_wave, fo);
-        else if (waves == 8u) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<8, true>), dim3(grid), dim3(512), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, per_wave, fo);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<4, true>), dim3(grid), dim3(256), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, per_wave, fo);
-        KCHK();
-        return BMX_OK;
-    }
-    // (round 3: a streaming form for operands of ANY block kinds was built and measured -- a wave owning a stretch of
-    // columns, sorted by load shape so that every pipelined loop issues a uniform number of loads, GAP blocks prefetched
-    // into registers and decoded from there: 52-58 us against the 45.9 us of this kernel on the 1 % mixed case at one to
-    // eight workgroups per CU (profiles/r03g, r03h); each of the nine shape loops fills and drains its own pipeline over
-    // ~4 columns.  Dropped.)
-    // mixed kinds, long vectors: the persistent form (one memory round trip per column, GAP blocks decoded from registers)
-    if (ctx->pair_loop != 0 && nblocks >= 2048u) {
+        const Stretch s = even_stretches(nblocks, waves, ctx->pair_wgs);
+        if (waves == 2u) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<2, true>), dim3(s.grid), dim3(128), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, s.per_wave, fo);
+        else if (waves == 8u) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<8, true>), dim3(s.grid), dim3(512), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, s.per_wave, fo);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_count_op2_stream<4, true>), dim3(s.grid), dim3(256), 0, ctx->stream, op, a->d_desc, b->d_desc, nblocks, s.per_wave, fo);
+    } else if (ctx->pair_loop != 0 && nblocks >= 2048u) {
+        // (round 3: a streaming form for operands of ANY block kinds was built and measured -- a wave owning a stretch of
+        // columns, sorted by load shape so that every pipelined loop issues a uniform number of loads, GAP blocks prefetched
+        // into registers and decoded from there: 52-58 us against the 45.9 us of this kernel on the 1 % mixed case at one to
+        // eight workgroups per CU (profiles/r03g, r03h); each of the nine shape loops fills and drains its own pipeline over
+        // ~4 columns.  Dropped.)
+        // mixed kinds, long vectors: the persistent form (one memory round trip per column, GAP blocks decoded from registers)
         const u32 wgs = (u32)(ctx->pair_loop > 0 ? ctx->pair_loop : 4);     // workgroups per CU = waves per SIMD
         const u32 grid = std::min<u32>((nblocks + 3u) / 4u, 256u * wgs);
         auto fn = ctx->pair_nt ? k_count_op2_loop<4, true> : k_count_op2_loop<4, false>;
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, op,
-                           a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, FoldOut{ctx->d_slots, ctx->d_done, out});
-        KCHK();
-        return BMX_OK;
-    }
-    hipLaunchKernelGGL(k_count_op2, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, op,
-                       a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, FoldOut{ctx->d_slots, ctx->d_done, out});
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, ctx->stream, op, a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, fo);
+    } else
+        hipLaunchKernelGGL(k_count_op2, dim3((nblocks + 3) / 4), dim3(256), 0, ctx->stream, op, a->d_desc, a->nblocks, b->d_desc, b->nblocks, nblocks, fo);
     KCHK();
     return BMX_OK;
 }
@@ -4524,12 +4525,10 @@ static int distance_pair_launch(bmx_ctx* ctx, const bmx_vec* a, const bmx_vec* b
     const uint32_t nblocks = std::max(a->nblocks, b->nblocks);
     if (!nblocks) { out[0] = out[1] = out[2] = 0; return BMX_OK; }
     const FoldOut fo{ctx->d_slots, ctx->d_done, out};
-    if (a->nblocks == b->nblocks && a->counts[BMX_BIT] == nblocks && b->counts[BMX_BIT] == nblocks && nblocks >= 2048u) {
-        const u32 total = 256u * 4u * (u32)std::max(ctx->pair_wgs, 1);     // the launch shape of the count_* stream
-        const u32 per_wave = (nblocks + total - 1u) / total;
-        const u32 grid = ((nblocks + per_wave - 1u) / per_wave + 3u) / 4u;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_distance_pair_stream<4, true>), dim3(grid), dim3(256), 0, ctx->stream,
-                           a->d_desc, b->d_desc, nblocks, per_wave, fo);
+    if (bits_only_pair(a, b)) {                                          // (the pair_stream key is not consulted here)
+        const Stretch s = even_stretches(nblocks, 4u, ctx->pair_wgs);    // the launch shape of the count_* stream
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_distance_pair_stream<4, true>), dim3(s.grid), dim3(256), 0, ctx->stream,
+                           a->d_desc, b->d_desc, nblocks, s.per_wave, fo);
     } else {
         const u32 grid = std::min<u32>((nblocks + 3u) / 4u, 1024u);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_distance_pair_loop<true>), dim3(grid), dim3(256), 0, ctx->stream,

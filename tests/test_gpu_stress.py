@@ -269,42 +269,77 @@ def test_block_kinds_follow_reference(ctx, port, seed):
     agg.set_optimization(False)
 
 
+# the two entries of a materialised pairwise operation: bmx_op2, and bmx_op2_dev + bmx_pending_wait
+_AND_ENTRIES = (("bit_and", lambda a, b: bm.bvector.bit_and(a, b)), ("op2_async", lambda a, b: bm.bvector.op2_async(bm.AND, a, b).wait()))
+
+
 def test_result_memory_is_what_the_result_holds(ctx, port):
     """a materialised result keeps only what it holds: the full-size slab is transient.  AND of two vectors that meet in
     3 of 400 blocks: the result owns 3 bit-blocks (compacted), its download moves 3 blocks, content = oracle; a result
-    that keeps 395 of 400 blocks stays in its slab (no second pass) and its download gathers the 395 live ones"""
-    nblk = 400
-    rng = np.random.default_rng(77)
-    wa = np.zeros(nblk * 2048, np.uint32); wb = np.zeros(nblk * 2048, np.uint32)
-    wa[:] = rng.integers(0, 1 << 32, wa.size, dtype=np.uint64).astype(np.uint32)
-    for nb in (5, 200, 399):
-        wb[nb * 2048:(nb + 1) * 2048] = rng.integers(0, 1 << 32, 2048, dtype=np.uint64).astype(np.uint32)
-    a, b = bm.bit_import_u32(ctx, wa, True), bm.bit_import_u32(ctx, wb, True)
-    pa, pb = port.import_words(wa, True, wa.size * 32), port.import_words(wb, True, wb.size * 32)
-    used = ctx.mem_used()
-    t = bm.bvector.bit_and(a, b)
-    i = t.info()
-    assert i["counts"][bm.BIT] == 3 and i["bit_slab_blocks"] == 3
-    assert ctx.mem_used() - used < 3 * 8192 + 2 * (2 << 20)            # not 400 x 8 KiB: three blocks + table (pool granules)
-    k, o, bits, gaps = t.block_table()
-    assert bits.size == 3 * 2048 and sorted(o[k == bm.BIT].tolist()) == [0, 1, 2]
-    e = port.op2(0, pa, pb, False)
-    assert (t.to_words() == e.to_words()).all() and k.tolist() == e.flatten()[0].tolist()
-    back = bm.bvector.from_block_table(ctx, nblk * 65536, k, o, bits, gaps)
-    assert (back.to_words() == e.to_words()).all()
-    # nearly full result: 395 of 400 blocks survive (b2 = all ones except five empty blocks)
-    wb2 = np.full(nblk * 2048, 0xFFFFFFFF, np.uint32)
-    for nb in (0, 7, 8, 123, 398):
-        wb2[nb * 2048:(nb + 1) * 2048] = 0
-    b2 = bm.bit_import_u32(ctx, wb2, True); pb2 = port.import_words(wb2, True, wb2.size * 32)
-    t2 = bm.bvector.bit_and(a, b2)
-    i2 = t2.info()
-    assert i2["counts"][bm.BIT] == 395 and i2["bit_slab_blocks"] == 395
-    k2, o2, bits2, gaps2 = t2.block_table()
-    assert bits2.size == 395 * 2048 and sorted(o2[k2 == bm.BIT].tolist()) == list(range(395))
-    e2 = port.op2(0, pa, pb2, False)
-    back2 = bm.bvector.from_block_table(ctx, nblk * 65536, k2, o2, bits2, gaps2)
-    assert (back2.to_words() == e2.to_words()).all() and (t2.to_words() == e2.to_words()).all()
+    that keeps 395 of 400 blocks stays in its slab (no second pass) and its download gathers the 395 live ones.  Both at 400
+    blocks (a wave per column) and at 2,100 (past the 2,048-block switch to the persistent kernel; the transient slab is then
+    17.2 MB), through the synchronous entry and through op2_async().wait().  Then operands of 2,100 GAP blocks (0.9 %: a few pass
+    the GAP limit and are bit-blocks) whose AND holds a few bit-blocks and ~2,075 GAP blocks of 1 % of the operands' GAP words: the
+    kernel lays the GAP results out into a slab sized at the operands' bound (9.6 MB), and the result keeps what it holds"""
+    for nblk in (400, 2100):
+        rng = np.random.default_rng(77)
+        wa = np.zeros(nblk * 2048, np.uint32); wb = np.zeros(nblk * 2048, np.uint32)
+        wa[:] = rng.integers(0, 1 << 32, wa.size, dtype=np.uint64).astype(np.uint32)
+        for nb in (5, 200, nblk - 1):
+            wb[nb * 2048:(nb + 1) * 2048] = rng.integers(0, 1 << 32, 2048, dtype=np.uint64).astype(np.uint32)
+        a, b = bm.bit_import_u32(ctx, wa, True), bm.bit_import_u32(ctx, wb, True)
+        pa, pb = port.import_words(wa, True, wa.size * 32), port.import_words(wb, True, wb.size * 32)
+        # nearly full result: all but five blocks survive (b2 = all ones except five empty blocks)
+        wb2 = np.full(nblk * 2048, 0xFFFFFFFF, np.uint32)
+        for nb in (0, 7, 8, 123, nblk - 2):
+            wb2[nb * 2048:(nb + 1) * 2048] = 0
+        b2 = bm.bit_import_u32(ctx, wb2, True); pb2 = port.import_words(wb2, True, wb2.size * 32)
+        e, e2 = port.op2(0, pa, pb, False), port.op2(0, pa, pb2, False)
+        ew, ek, ew2 = e.to_words(), e.flatten()[0].tolist(), e2.to_words()
+        for name, and_ in _AND_ENTRIES:
+            t = None                                                          # (the other entry's result is not this one's credit)
+            used = ctx.mem_used()
+            t = and_(a, b)
+            i = t.info()
+            assert i["counts"][bm.BIT] == 3 and i["bit_slab_blocks"] == 3, (nblk, name, i)
+            assert ctx.mem_used() - used < 3 * 8192 + 2 * (2 << 20), (nblk, name)   # not nblk x 8 KiB: three blocks + table (pool granules)
+            k, o, bits, gaps = t.block_table()
+            assert bits.size == 3 * 2048 and sorted(o[k == bm.BIT].tolist()) == [0, 1, 2], (nblk, name)
+            assert (t.to_words() == ew).all() and k.tolist() == ek, (nblk, name)
+            back = bm.bvector.from_block_table(ctx, nblk * 65536, k, o, bits, gaps)
+            assert (back.to_words() == ew).all(), (nblk, name)
+            t2 = and_(a, b2)
+            i2 = t2.info()
+            assert i2["counts"][bm.BIT] == nblk - 5 and i2["bit_slab_blocks"] == nblk - 5, (nblk, name, i2)
+            k2, o2, bits2, gaps2 = t2.block_table()
+            assert bits2.size == (nblk - 5) * 2048 and sorted(o2[k2 == bm.BIT].tolist()) == list(range(nblk - 5)), (nblk, name)
+            back2 = bm.bvector.from_block_table(ctx, nblk * 65536, k2, o2, bits2, gaps2)
+            assert (back2.to_words() == ew2).all() and (t2.to_words() == ew2).all(), (nblk, name)
+            if nblk == 400 and name == "bit_and":
+                keep = (a, b, t2, k2, o2, e2)
+    # operands of GAP blocks, 2,100 of them: the kernel of either entry lays its GAP results out, the slab at the bound is trimmed
+    nblk = 2100
+    wga, wgb = (port.gen_words(77, v, 580, nblk * 65536) for v in (1, 2))
+    ga, gb = bm.bit_import_u32(ctx, wga, True), bm.bit_import_u32(ctx, wgb, True)
+    eg = port.op2(0, port.import_words(wga, True, nblk * 65536), port.import_words(wgb, True, nblk * 65536), False)
+    egw, egk = eg.to_words(), eg.flatten()[0]
+    live, operand_gap_words = int((egk == bm.BIT).sum()), ga.info()["gap_words"] + gb.info()["gap_words"]
+    assert live == 13 and int((egk == bm.GAP).sum()) == 2075 and operand_gap_words > 4_500_000      # (the oracle's, for these seeds)
+    redzone = 8192 if ctx.redzone_check()["enabled"] else 0
+    for name, and_ in _AND_ENTRIES:
+        t = and_(ga, gb)                                                    # (the context's scratch has grown to this shape)
+        t = None
+        used = ctx.mem_used()
+        t = and_(ga, gb)
+        grew = ctx.mem_used() - used
+        i = t.info()
+        print(name, "GAP case: grew", grew, "info", i)
+        assert (t.block_table()[0] == egk).all() and (t.to_words() == egw).all(), name
+        assert i["counts"][bm.BIT] == live and i["bit_slab_blocks"] == live and i["gap_words"] * 20 < operand_gap_words, (name, i)
+        # what it holds, with the pool's best-fit slack (25 %) and one 2-MiB granule for each of the descriptor table, the bit slab,
+        # the GAP slab and the ordinals; the GAP slab at the operands' bound alone is 9.6 MB
+        assert grew < 1.25 * (live * 8192 + 2 * i["gap_words"] + 64 + 12 * nblk) + 4 * ((2 << 20) + redzone), (name, grew, i)
+    a, b, t2, k2, o2, e2 = keep
     # a clone of a slab with unused slots keeps the ordinals; pipeline results over many groups stay small
     t3 = bm.bvector.bit_and(t2, t2)                                      # aliasing: block-for-block copy (src/bm.h:6191)
     assert (t3.to_words() == e2.to_words()).all() and t3.block_table()[1][k2 == bm.BIT].tolist() == o2[k2 == bm.BIT].tolist()
