@@ -1907,7 +1907,23 @@ int bmx_vec_operand_bytes(bmx_ctx* ctx, const bmx_vec* v, uint64_t* bytes)
     return BMX_OK;
 ABI_END }
 
-// sorted positions of the set bits: device compaction (bmx_kernels6.h k_block_counts / k_rs_scan / k_expand_indices)
+// The ones of every block of a non-empty v (d_bc: 4 bytes a block), the ones up to and including every block (d_rc: 8 bytes a block)
+// and their total, read on the host: one synchronise.  bmx_rs_build has its own sequence (k_rs_build produces its counts).
+static int running_counts(bmx_ctx* ctx, const bmx_vec* v, DevBuf& d_bc, DevBuf& d_rc, uint64_t* total)
+{
+    int rc;
+    const uint32_t nb = v->nblocks;
+    if ((rc = dmalloc(ctx, &d_bc.p, (size_t)nb * 4)) || (rc = dmalloc(ctx, &d_rc.p, (size_t)nb * 8))) return rc;
+    hipLaunchKernelGGL(k_block_counts, dim3((nb + 3) / 4), dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nb, (u32*)d_bc);
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, nb, (u64*)d_rc, ctx->d_small);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *total = ctx->h_small[0];
+    return BMX_OK;
+}
+
+// sorted positions of the set bits: device compaction (running_counts, then bmx_kernels6.h k_expand_indices)
 static int vec_indices_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out, bool out_is_host, uint64_t cap, uint64_t* n)
 {
     ARGCHK(ctx && v && v->ctx == ctx && n && (width == 4 || width == 8) && (cap == 0 || out));
@@ -1917,14 +1933,9 @@ static int vec_indices_impl(bmx_ctx* ctx, const bmx_vec* v, int width, void* out
     if (!nblocks) return BMX_OK;
     if (width == 4 && (uint64_t)nblocks > 65536ull) { g_last_error = "32-bit positions cannot address this vector: use width 8"; return BMX_ERR_RANGE; }
     DevBuf d_rc(ctx), d_bc(ctx), host_out(ctx);                    // (given back in reverse: host_out, d_bc, d_rc)
-    if ((rc = dmalloc(ctx, &d_bc.p, (size_t)nblocks * 4)) || (rc = dmalloc(ctx, &d_rc.p, (size_t)nblocks * 8))) return rc;
     const dim3 wgrid((nblocks + 3) / 4);
-    hipLaunchKernelGGL(k_block_counts, wgrid, dim3(256), 0, ctx->stream, (const u64*)v->d_desc, nblocks, (u32*)d_bc);
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, nblocks, (u64*)d_rc, ctx->d_small);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    const uint64_t total = ctx->h_small[0];
+    uint64_t total = 0;
+    if ((rc = running_counts(ctx, v, d_bc, d_rc, &total))) return rc;
     *n = total;
     if (total > cap) { g_last_error = "output buffer too small for the positions (n holds the number needed)"; return BMX_ERR_RANGE; }
     if (!total) return BMX_OK;
@@ -4044,9 +4055,176 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
     return BMX_OK;
 ABI_END }
 
+} // extern "C"
+
 // ---------------------------------------------------------------------------
 // rank / select
 // ---------------------------------------------------------------------------
+// ---- the index build: bmx_rs_build runs the stages rs_* below in order; each stands next to the policy that decides whether and
+// in what shape its structure is built.  The policies make no HIP call. ----
+// One pass of the build that reports through a flag word: clear the word at d_small + 32, run the caller's launches, copy the word
+// back, synchronise; *flag = h_small[32].  `what` names the pass in the error text.
+template <class Launches> static int rs_flagged(bmx_ctx* ctx, const char* what, Launches&& launches, uint64_t* flag)
+{
+    hipError_t e = hipMemsetAsync(ctx->d_small + 32, 0, 8, ctx->stream);
+    if (e == hipSuccess) { launches(); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_small + 32, ctx->d_small + 32, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    *flag = ctx->h_small[32];
+    return e == hipSuccess ? BMX_OK : fail_hip(e, what, __LINE__);
+}
+
+// Block tables (ones per block and per sub-block, the cumulative rows, the GAP index), the running counts (their total lands in
+// d_small[0]: bmx_rs_build reads it once, after the rank lines are enqueued) and the samples of the running counts, at most 2,048
+static int rs_tables(bmx_ctx* ctx, const bmx_vec* v, bmx_rs* rs)
+{
+    int rc;
+    const uint32_t n = std::max<uint32_t>(v->nblocks, 1);
+    const size_t b1 = (size_t)n * 4, b2 = (size_t)n * 8, b3 = (size_t)n * 8, b4 = (size_t)n * 128;
+    if ((rc = dmalloc(ctx, (void**)&rs->d_bcount, b1)) || (rc = dmalloc(ctx, (void**)&rs->d_sub, b2)) ||
+        (rc = dmalloc(ctx, (void**)&rs->d_rcount, b3)) || (rc = dmalloc(ctx, (void**)&rs->d_cum, b4)) ||
+        (rc = dmalloc(ctx, (void**)&rs->d_gidx, b4))) return rc;
+    rs->bytes = b1 + b2 + b3 + 2 * b4;
+    if (!v->nblocks) return BMX_OK;
+    hipLaunchKernelGGL(k_rs_build, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream,
+                       v->d_desc, v->nblocks, rs->d_bcount, rs->d_sub, rs->d_cum, rs->d_gidx);
+    KCHK();
+    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, rs->d_bcount, v->nblocks, rs->d_rcount, ctx->d_small);
+    KCHK();
+    uint32_t shift = 0;
+    while (((v->nblocks + (1u << shift) - 1u) >> shift) > 2048u) ++shift;
+    rs->sample_shift = shift; rs->nsamples = (v->nblocks + (1u << shift) - 1u) >> shift;
+    if ((rc = dmalloc(ctx, (void**)&rs->d_sample, (size_t)rs->nsamples * 8))) return rc;
+    hipLaunchKernelGGL(k_rs_sample, dim3((rs->nsamples + 255) / 256), dim3(256), 0, ctx->stream,
+                       rs->d_rcount, v->nblocks, shift, rs->nsamples, rs->d_sample);
+    KCHK();
+    return BMX_OK;
+}
+
+// rank lines (bmx_kernels6.h): the vector once more, interleaved with its running counts -- one line per rank query.
+// Memory policy (rs_lines 1): they are built where they cost no more than 2 x what the vector itself holds on the
+// device, i.e. for vectors with bit-blocks in more than about half of their block columns (configs[3]'s 66%); a sparse vector (GAP / NULL / FULL blocks: a 4e9-bit
+// operand of configs[4] is 3.4 MB, its lines would be 539 MB) keeps the table kernels (k_rank_l / k_select_l over the
+// running counts, src/bmrs.h:39-155 is 0.7 MB for such a vector too).  Line numbers are 32-bit: 69 lines per block
+// pass 2^32 at 62.2 M blocks = 510 GB of bit-blocks under this policy, more than a device holds; refused anyway.
+static size_t rank_lines_bytes(const bmx_vec* v) { return (size_t)v->nblocks * RL_LINES * 128u; }
+static bool rank_lines_wanted(const bmx_ctx* ctx, const bmx_vec* v)
+{
+    const bool lines_fit = (uint64_t)v->nblocks * RL_LINES < 0xFFFFFFFFull;
+    return lines_fit && (ctx->rs_lines == 2 || (ctx->rs_lines == 1 && (double)rank_lines_bytes(v) <= 2.0 * (double)v->bytes));
+}
+static int rs_rank_lines(bmx_ctx* ctx, const bmx_vec* v, bmx_rs* rs)
+{
+    if (!rank_lines_wanted(ctx, v)) return BMX_OK;
+    const size_t bl = rank_lines_bytes(v), bd = (size_t)v->nblocks * 16u;     // the lines, the octant directory
+    int rc;
+    if ((rc = dmalloc(ctx, (void**)&rs->d_lines, bl)) || (rc = dmalloc(ctx, (void**)&rs->d_dir8, bd))) return rc;
+    rs->bytes += bl + bd;
+    hipLaunchKernelGGL(k_rs_lines, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream,
+                       v->d_desc, v->nblocks, (const u64*)rs->d_rcount, rs->d_lines, rs->d_dir8);
+    KCHK();
+    return BMX_OK;
+}
+
+// select lines (bmx_kernels11.h): the ones' positions, 60 (16-bit offsets) or 30 (32-bit) per 128-byte line.  Memory
+// policy (rs_select_sel -1): where they cost no more than 2 x what the vector and its rank lines hold on the device.
+// The 16-bit form is tried unless the average spacing of the ones already says that 60 of them span half a block.
+struct SelLinesPolicy { double budget; int first_bits; };
+static SelLinesPolicy select_lines_policy(const bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs)
+{
+    const double budget = 2.0 * ((double)v->bytes + (rs->d_lines ? (double)rank_lines_bytes(v) : 0.0));
+    const bool try16 = ctx->rs_select_sel != 2 && (double)v->nblocks * 65536.0 / (double)rs->count * 60.0 < 32768.0;
+    return {budget, try16 ? 16 : 32};
+}
+static int rs_select_lines(bmx_ctx* ctx, const bmx_vec* v, bmx_rs* rs)
+{
+    if (!rs->count || ctx->rs_select_sel == 0) return BMX_OK;
+    const SelLinesPolicy pol = select_lines_policy(ctx, v, rs);
+    for (int bits = pol.first_bits; bits <= 32 && !rs->d_sel; bits += 16) {
+        const uint32_t K = bits == 16 ? 60u : 30u;
+        const uint64_t nsel = (rs->count + K - 1u) / K;
+        const size_t sb = (size_t)nsel * SL_BYTES;
+        if (ctx->rs_select_sel == -1 && (double)sb > pol.budget) break;
+        DevBuf d(ctx);
+        if (dmalloc(ctx, &d.p, sb) != BMX_OK) break;                 // (an optional index: the directory kernels serve)
+        const auto fns = bits == 16 ? std::make_pair(k_rs_sel_build<u16>, k_rs_sel_check<u16>) : std::make_pair(k_rs_sel_build<u32>, k_rs_sel_check<u32>);
+        uint64_t too_wide = 0;
+        int rc = rs_flagged(ctx, "select lines", [&] {
+            hipLaunchKernelGGL(fns.first, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, (u8*)d);
+            hipLaunchKernelGGL(fns.second, dim3((u32)((nsel + 255u) / 256u)), dim3(256), 0, ctx->stream, (const u8*)d, (u64)nsel, (u64)rs->count, (const u64*)rs->d_rcount, v->nblocks, (u32*)(ctx->d_small + 32));
+        }, &too_wide);
+        if (rc) return rc;
+        if (too_wide) { d.reset(); continue; }                       // a line spans >= 2^bits bits: the wider form
+        rs->d_sel = (u8*)d.release(); rs->sel_bits = (uint32_t)bits; rs->sel_lines = nsel; rs->bytes += sb;
+    }
+    return BMX_OK;
+}
+
+// select directory over the rank lines: the line of every 2^shift-th one (+ sentinel); k_select_sdir.  The shift is rs_sdir_shift,
+// or automatic: 2^shift next to 10 x (ones per line); either way it grows until the directory stays under 8 MB.
+static uint32_t sdir_shift_for(const bmx_ctx* ctx, uint64_t count, uint64_t nlines)
+{
+    uint32_t sh = (uint32_t)ctx->rs_sdir_shift;
+    if (ctx->rs_sdir_shift <= 0) {
+        const double want = 10.0 * (double)count / (double)nlines;
+        sh = 6u; while (sh < 20u && (double)(1ull << sh) * 1.4142 < want) ++sh;
+    }
+    while (((count >> sh) + 2ull) * 4ull > (8ull << 20) && sh < 24u) ++sh;
+    return sh;
+}
+static int rs_select_dir(bmx_ctx* ctx, const bmx_vec* v, bmx_rs* rs)
+{
+    if (!rs->d_lines || !rs->count) return BMX_OK;
+    const uint64_t nlines = (uint64_t)v->nblocks * RL_LINES;
+    const uint32_t sh = sdir_shift_for(ctx, rs->count, nlines);
+    rs->sdir_shift = sh; rs->sdir_entries = ((rs->count + (1ull << sh) - 1ull) >> sh) + 1ull;
+    if (int rc = dmalloc(ctx, (void**)&rs->d_sdir, (size_t)rs->sdir_entries * 4u + 16u)) return rc;
+    rs->bytes += (size_t)rs->sdir_entries * 4u;
+    hipLaunchKernelGGL(k_rs_sdir, dim3((u32)((nlines + 255u) / 256u)), dim3(256), 0, ctx->stream,
+                       (const u32*)rs->d_lines, (u64)nlines, (u64)rs->count, sh, rs->d_sdir, (u64)rs->sdir_entries);
+    KCHK();
+    return BMX_OK;
+}
+
+// the directory's summary for LDS (k_select_top): one entry per 2^shift ones, at most 65,535 + the sentinel; an entry
+// is the position of its one to 1 / 2^fb of a line (fb <= 3: as fine as the 16-bit offsets of a group of 64 entries allow)
+struct StopShape { uint32_t shift, n_top; };
+static StopShape stop_shape(uint64_t count, uint32_t sdir_shift)
+{
+    uint32_t ssh = sdir_shift;
+    while (((count + (1ull << ssh) - 1ull) >> ssh) + 1ull > STOP_ENTRIES && ssh < 40u) ++ssh;
+    return {ssh, (uint32_t)(((count + (1ull << ssh) - 1ull) >> ssh) + 1ull)};
+}
+static int rs_select_summary(bmx_ctx* ctx, const bmx_vec* v, bmx_rs* rs)
+{
+    if (!rs->d_sdir) return BMX_OK;
+    const uint64_t nlines = (uint64_t)v->nblocks * RL_LINES;
+    const StopShape s = stop_shape(rs->count, rs->sdir_shift);
+    DevBuf d_p8(ctx);
+    if (nlines >= (1ull << 28) || dmalloc(ctx, &d_p8.p, (size_t)s.n_top * 4u + 64u) != BMX_OK) return BMX_OK;
+    if (int rc = dmalloc(ctx, (void**)&rs->d_stop, STOP_BYTES + 64u)) return rc;
+    hipError_t e = hipMemsetAsync(rs->d_stop, 0, STOP_BYTES + 64u, ctx->stream);
+    if (e != hipSuccess) return fail_hip(e, "select summary", __LINE__);
+    uint64_t widest = 0;                                                  // of a group of 64 entries at the most, in eighths of a line
+    int rc = rs_flagged(ctx, "select summary", [&] {
+        hipLaunchKernelGGL(k_rs_stop_pos, dim3((s.n_top + 255u) / 256u), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_sdir, (u64)rs->sdir_entries,
+                           rs->sdir_shift, s.shift, s.n_top, (u64)rs->count, (u32*)d_p8);
+        hipLaunchKernelGGL(k_rs_stop_range, dim3((s.n_top / STOP_GROUP + 256u) / 256u), dim3(256), 0, ctx->stream, (const u32*)d_p8, s.n_top, (u32*)(ctx->d_small + 32));
+    }, &widest);
+    if (rc) return rc;
+    const uint32_t spread = (uint32_t)widest;
+    uint32_t fb = 3u;
+    while (fb > 0u && (spread >> (3u - fb)) > 65000u) --fb;
+    if ((spread >> (3u - fb)) > 65000u) { dfree(ctx, rs->d_stop); rs->d_stop = nullptr; return BMX_OK; }   // (64 entries spread over more than 65,000 lines somewhere: the global directory serves)
+    hipLaunchKernelGGL(k_rs_stop_pack, dim3((s.n_top + 255u) / 256u), dim3(256), 0, ctx->stream, (const u32*)d_p8, s.n_top, 3u - fb, rs->d_stop, (u16*)(rs->d_stop + STOP_BASES));
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "k_rs_stop_pack", __LINE__);
+    rs->stop_shift = s.shift; rs->stop_fb = fb; rs->bytes += STOP_BYTES;
+    return BMX_OK;
+}
+
+extern "C" {
+
 int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
 { ABI_TRY
     ARGCHK(ctx && v && out && v->ctx == ctx);
@@ -4054,121 +4232,14 @@ int bmx_rs_build(bmx_ctx* ctx, const bmx_vec* v, bmx_rs** out)
     int rc = set_dev(ctx); if (rc) return rc;
     Owned<bmx_rs> rs(new bmx_rs());
     rs->ctx = ctx; rs->nblocks = v->nblocks;
-    uint32_t n = std::max<uint32_t>(v->nblocks, 1);
-    size_t b1 = (size_t)n * 4, b2 = (size_t)n * 8, b3 = (size_t)n * 8, b4 = (size_t)n * 128;
-    if ((rc = dmalloc(ctx, (void**)&rs->d_bcount, b1)) || (rc = dmalloc(ctx, (void**)&rs->d_sub, b2)) ||
-        (rc = dmalloc(ctx, (void**)&rs->d_rcount, b3)) || (rc = dmalloc(ctx, (void**)&rs->d_cum, b4)) ||
-        (rc = dmalloc(ctx, (void**)&rs->d_gidx, b4))) return rc;
-    rs->bytes = b1 + b2 + b3 + 2 * b4;
+    if ((rc = rs_tables(ctx, v, rs.get()))) return rc;
     if (v->nblocks) {
-        hipLaunchKernelGGL(k_rs_build, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                           v->d_desc, v->nblocks, rs->d_bcount, rs->d_sub, rs->d_cum, rs->d_gidx);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, rs->d_bcount, v->nblocks, rs->d_rcount, ctx->d_small);
-        HIPCHK(hipGetLastError());
-        uint32_t shift = 0;
-        while (((v->nblocks + (1u << shift) - 1u) >> shift) > 2048u) ++shift;
-        rs->sample_shift = shift; rs->nsamples = (v->nblocks + (1u << shift) - 1u) >> shift;
-        if ((rc = dmalloc(ctx, (void**)&rs->d_sample, (size_t)rs->nsamples * 8))) return rc;
-        hipLaunchKernelGGL(k_rs_sample, dim3((rs->nsamples + 255) / 256), dim3(256), 0, ctx->stream,
-                           rs->d_rcount, v->nblocks, shift, rs->nsamples, rs->d_sample);
-        HIPCHK(hipGetLastError());
-        // rank lines (bmx_kernels6.h): the vector once more, interleaved with its running counts -- one line per rank query.
-        // Memory policy (rs_lines 1): they are built where they cost no more than 2 x what the vector itself holds on the
-        // device, i.e. for vectors with bit-blocks in more than about half of their block columns (configs[3]'s 66%); a sparse vector (GAP / NULL / FULL blocks: a 4e9-bit
-        // operand of configs[4] is 3.4 MB, its lines would be 539 MB) keeps the table kernels (k_rank_l / k_select_l over the
-        // running counts, src/bmrs.h:39-155 is 0.7 MB for such a vector too).  Line numbers are 32-bit: 69 lines per block
-        // pass 2^32 at 62.2 M blocks = 510 GB of bit-blocks under this policy, more than a device holds; refused anyway.
-        const size_t lines_bytes = (size_t)v->nblocks * RL_LINES * 128u;
-        const bool lines_fit = (uint64_t)v->nblocks * RL_LINES < 0xFFFFFFFFull;
-        const bool want_lines = lines_fit && (ctx->rs_lines == 2 || (ctx->rs_lines == 1 && (double)lines_bytes <= 2.0 * (double)v->bytes));
-        if (want_lines) {
-            size_t bl = lines_bytes;
-            if ((rc = dmalloc(ctx, (void**)&rs->d_lines, bl)) || (rc = dmalloc(ctx, (void**)&rs->d_dir8, (size_t)v->nblocks * 16u))) return rc;
-            rs->bytes += bl + (size_t)v->nblocks * 16u;
-            hipLaunchKernelGGL(k_rs_lines, dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream,
-                               v->d_desc, v->nblocks, (const u64*)rs->d_rcount, rs->d_lines, rs->d_dir8);
-            HIPCHK(hipGetLastError());
-        }
+        if ((rc = rs_rank_lines(ctx, v, rs.get()))) return rc;
         HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         rs->count = ctx->h_small[0];
-        if (rs->count && ctx->rs_select_sel != 0) {
-            // select lines (bmx_kernels11.h): the ones' positions, 60 (16-bit offsets) or 30 (32-bit) per 128-byte line.  Memory
-            // policy (rs_select_sel -1): where they cost no more than 2 x what the vector and its rank lines hold on the device.
-            // The 16-bit form is tried unless the average spacing of the ones already says that 60 of them span half a block.
-            const double budget = 2.0 * ((double)v->bytes + (rs->d_lines ? (double)lines_bytes : 0.0));
-            const bool try16 = ctx->rs_select_sel != 2 && (double)v->nblocks * 65536.0 / (double)rs->count * 60.0 < 32768.0;
-            for (int bits = try16 ? 16 : 32; bits <= 32 && !rs->d_sel; bits += 16) {
-                const uint32_t K = bits == 16 ? 60u : 30u;
-                const uint64_t nsel = (rs->count + K - 1u) / K;
-                const size_t sb = (size_t)nsel * SL_BYTES;
-                if (ctx->rs_select_sel == -1 && (double)sb > budget) break;
-                DevBuf d(ctx);
-                if (dmalloc(ctx, &d.p, sb) != BMX_OK) break;                 // (an optional index: the directory kernels serve)
-                HIPCHK(hipMemsetAsync(ctx->d_small + 32, 0, 8, ctx->stream));
-                if (bits == 16) {
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_build<u16>), dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, (u8*)d);
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_check<u16>), dim3((u32)((nsel + 255u) / 256u)), dim3(256), 0, ctx->stream, (const u8*)d, (u64)nsel, (u64)rs->count, (const u64*)rs->d_rcount, v->nblocks, (u32*)(ctx->d_small + 32));
-                } else {
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_build<u32>), dim3((v->nblocks + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, (const u64*)rs->d_rcount, (u8*)d);
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rs_sel_check<u32>), dim3((u32)((nsel + 255u) / 256u)), dim3(256), 0, ctx->stream, (const u8*)d, (u64)nsel, (u64)rs->count, (const u64*)rs->d_rcount, v->nblocks, (u32*)(ctx->d_small + 32));
-                }
-                hipError_t e_ = hipGetLastError();
-                if (e_ == hipSuccess) e_ = hipMemcpyAsync(ctx->h_small + 32, ctx->d_small + 32, 8, hipMemcpyDeviceToHost, ctx->stream);
-                if (e_ == hipSuccess) e_ = hipStreamSynchronize(ctx->stream);
-                if (e_ != hipSuccess) return fail_hip(e_, "select lines", __LINE__);
-                if (ctx->h_small[32] != 0) { d.reset(); continue; }          // a line spans >= 2^bits bits: the wider form
-                rs->d_sel = (u8*)d.release(); rs->sel_bits = (uint32_t)bits; rs->sel_lines = nsel; rs->bytes += sb;
-            }
-        }
-        if (rs->d_lines && rs->count) {
-            // select directory over the lines: the line of every 2^shift-th one (+ sentinel); k_select_sdir
-            const uint64_t nlines = (uint64_t)v->nblocks * RL_LINES;
-            uint32_t sh = (uint32_t)ctx->rs_sdir_shift;
-            if (ctx->rs_sdir_shift <= 0) {                        // automatic: 2^sh next to 10 x (ones per line)
-                const double want = 10.0 * (double)rs->count / (double)nlines;
-                sh = 6u; while (sh < 20u && (double)(1ull << sh) * 1.4142 < want) ++sh;
-            }
-            while (((rs->count >> sh) + 2ull) * 4ull > (8ull << 20) && sh < 24u) ++sh;
-            rs->sdir_shift = sh; rs->sdir_entries = ((rs->count + (1ull << sh) - 1ull) >> sh) + 1ull;
-            if ((rc = dmalloc(ctx, (void**)&rs->d_sdir, (size_t)rs->sdir_entries * 4u + 16u))) return rc;
-            rs->bytes += (size_t)rs->sdir_entries * 4u;
-            hipLaunchKernelGGL(k_rs_sdir, dim3((u32)((nlines + 255u) / 256u)), dim3(256), 0, ctx->stream,
-                               (const u32*)rs->d_lines, (u64)nlines, (u64)rs->count, sh, rs->d_sdir, (u64)rs->sdir_entries);
-            HIPCHK(hipGetLastError());
-            // the directory's summary for LDS (k_select_top): one entry per 2^stop_shift ones, at most 65,535 + the sentinel; an entry
-            // is the position of its one to 1 / 2^fb of a line (fb <= 3: as fine as the 16-bit offsets of a group of 64 entries allow)
-            uint32_t ssh = sh;
-            while (((rs->count + (1ull << ssh) - 1ull) >> ssh) + 1ull > STOP_ENTRIES && ssh < 40u) ++ssh;
-            const uint32_t n_top = (uint32_t)(((rs->count + (1ull << ssh) - 1ull) >> ssh) + 1ull);
-            DevBuf d_p8(ctx);
-            if (nlines < (1ull << 28) && dmalloc(ctx, &d_p8.p, (size_t)n_top * 4u + 64u) == BMX_OK) {
-                if ((rc = dmalloc(ctx, (void**)&rs->d_stop, STOP_BYTES + 64u))) return rc;
-                hipError_t e_ = hipMemsetAsync(rs->d_stop, 0, STOP_BYTES + 64u, ctx->stream);
-                if (e_ == hipSuccess) e_ = hipMemsetAsync(ctx->d_small + 32, 0, 8, ctx->stream);
-                if (e_ == hipSuccess) {
-                    hipLaunchKernelGGL(k_rs_stop_pos, dim3((n_top + 255u) / 256u), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_sdir, (u64)rs->sdir_entries,
-                                       sh, ssh, n_top, (u64)rs->count, (u32*)d_p8);
-                    hipLaunchKernelGGL(k_rs_stop_range, dim3((n_top / STOP_GROUP + 256u) / 256u), dim3(256), 0, ctx->stream, (const u32*)d_p8, n_top, (u32*)(ctx->d_small + 32));
-                    e_ = hipGetLastError();
-                }
-                if (e_ == hipSuccess) e_ = hipMemcpyAsync(ctx->h_small + 32, ctx->d_small + 32, 8, hipMemcpyDeviceToHost, ctx->stream);
-                if (e_ == hipSuccess) e_ = hipStreamSynchronize(ctx->stream);
-                if (e_ != hipSuccess) return fail_hip(e_, "select summary", __LINE__);
-                const uint32_t spread = (uint32_t)ctx->h_small[32];          // in eighths of a line
-                uint32_t fb = 3u;
-                while (fb > 0u && (spread >> (3u - fb)) > 65000u) --fb;
-                if ((spread >> (3u - fb)) > 65000u) { dfree(ctx, rs->d_stop); rs->d_stop = nullptr; }   // (64 entries spread over more than 65,000 lines somewhere: the global directory serves)
-                else {
-                    hipLaunchKernelGGL(k_rs_stop_pack, dim3((n_top + 255u) / 256u), dim3(256), 0, ctx->stream, (const u32*)d_p8, n_top, 3u - fb, rs->d_stop, (u16*)(rs->d_stop + STOP_BASES));
-                    e_ = hipGetLastError();
-                    if (e_ != hipSuccess) return fail_hip(e_, "k_rs_stop_pack", __LINE__);
-                    rs->stop_shift = ssh; rs->stop_fb = fb; rs->bytes += STOP_BYTES;
-                }
-                d_p8.reset();
-            }
-        }
+        if ((rc = rs_select_lines(ctx, v, rs.get())) || (rc = rs_select_dir(ctx, v, rs.get())) ||
+            (rc = rs_select_summary(ctx, v, rs.get()))) return rc;
     }
     *out = rs.release();
     return BMX_OK;
@@ -4204,28 +4275,131 @@ int bmx_rs_export(bmx_ctx* ctx, const bmx_rs* rs, uint32_t* bcount, uint64_t* su
     return BMX_OK;
 ABI_END }
 
+} // extern "C"
+
+// ---- rank / select queries: which kernel serves a batch and in what shape (rank_plan / select_plan: no HIP call), and its launch
+// (rank_launch / select_launch: the only places that name the query kernels) ----
 #define RS_LANES_DEFAULT 2
 #define RS_SELECT_LANES_DEFAULT 4
-static u32 query_grid(size_t q) { return (u32)std::min<size_t>((q * 8 + 255) / 256, 256u * 16u); }
+enum RankFamily { RANK_LINES, RANK_TABLES };
+enum SelectFamily { SELECT_SEL, SELECT_TOP, SELECT_SDIR, SELECT_LINES, SELECT_TABLES };
+struct RankPlan { RankFamily family; int lpq; u32 grid, wg; size_t lds; };          // lpq: lanes per query
+struct SelectPlan { SelectFamily family; int lpq; u32 grid, wg; size_t lds; };
+static u32 capped_grid(size_t items, u32 per_wg, u32 cap) { return (u32)std::min<size_t>((items + per_wg - 1) / per_wg, cap); }
+
+// Rank.  lpq = rs_lanes, or automatic (0): 2 from 65,536 queries, 8 below (batches too small to fill the chip keep the 8-lane kernel).
+//   rank lines exist and lpq != 8 : k_rank_lines<lpq>
+//   otherwise                     : k_rank_l<2>, k_rank_l<4> or k_rank (8 lanes) over the block tables
+// Grid min((q x lpq + 255) / 256, 4,096), 256 threads.
+static RankPlan rank_plan(const bmx_ctx* ctx, const bmx_rs* rs, size_t q)
+{
+    const int lpq = ctx->rs_lanes ? ctx->rs_lanes : (q >= (1u << 16) ? RS_LANES_DEFAULT : 8);
+    return {rs->d_lines && lpq != 8 ? RANK_LINES : RANK_TABLES, lpq, capped_grid(q * (size_t)lpq, 256u, 256u * 16u), 256u, 0};
+}
+static void rank_launch(bmx_ctx* ctx, const RankPlan& pl, const bmx_vec* v, const bmx_rs* rs, const uint64_t* d_n, size_t q, uint64_t* d_out)
+{
+    if (pl.family == RANK_LINES) {
+        auto fn = pl.lpq == 2 ? k_rank_lines<2> : k_rank_lines<4>;
+        hipLaunchKernelGGL(fn, dim3(pl.grid), dim3(pl.wg), pl.lds, ctx->stream, (const u32*)rs->d_lines, v->nblocks, rs->count, (const u64*)d_n, (u64)q, (u64*)d_out);
+    } else {
+        auto fn = k_rank;                                          // (assigned, not a nested ?: -- that instantiates <4> before <2>)
+        if (pl.lpq == 2) fn = k_rank_l<2>; else if (pl.lpq == 4) fn = k_rank_l<4>;
+        hipLaunchKernelGGL(fn, dim3(pl.grid), dim3(pl.wg), pl.lds, ctx->stream, v->d_desc, v->nblocks,
+                           rs->d_rcount, rs->d_cum, rs->d_gidx, rs->count, (const u64*)d_n, (u64)q, (u64*)d_out);
+    }
+}
+
+// Select, in this order:
+//   1. select lines: d_sel exists and rs_select_sel != 0 : k_select_sel<u16|u32> by the index's sel_bits -- one lane and one 128-byte
+//      line per query, no search (bmx_kernels11.h); any batch size, any order, rs_lanes not consulted.  Grid min((q + 511) / 512, 2,048),
+//      256 threads.
+//   2. lanes: lpq = rs_lanes, or automatic (0): 4 from 65,536 queries, 8 below.  top_ok = the summary and the directory exist
+//      (d_stop, d_sdir), rs_select_lines == 2, rs_select_top != 0, (rs_select_top == 1, or q >= 2^22 and no sorted hint), q < 2^32,
+//      max_lds_bytes >= STOP_BYTES + 16,384.  Automatic lanes become 2 where top_ok, and where rs_sorted_hint and q >= 65,536.
+//   3. summary in LDS: top_ok and lpq != 8 : k_select_top<lpq>, one 1024-thread workgroup per CU (129 KiB of LDS each:
+//      STOP_BYTES + a queue of 64 parked queries for each of 16 waves), one global read per query; grid min((q x lpq + 1,023) / 1,024, 256).
+//      The only launch behind a hipFuncSetAttribute.
+//   4. select directory: d_sdir, lpq != 8, rs_select_lines == 2 : k_select_sdir<lpq>
+//   5. rank lines: d_lines, lpq != 8, rs_select_lines != 0      : k_select_lines<lpq>
+//   6. tables: otherwise k_select_l<2>, k_select_l<4> or k_select (8 lanes)
+// 4 to 6: grid min((q x lpq + 255) / 256, 4,096), 256 threads.  So a forced rs_lanes 8 skips the summary, the directory and the lines
+// and lands on k_select.
+// Why 3 from 4 M queries (profiles/r05_select): 10 M random selects on configs[3] 0.377 ms against 0.416 / 0.436 for the
+// global-directory kernel with four / two lanes, 100 M: 3.63 against 4.09; at 1 M the 129 KiB every workgroup copies first cost more than
+// they save: 0.058 against 0.044.  Why the sorted hint (ranks the caller says arrive in ascending order, cursor-style enumeration):
+// neighbours share lines and directory entries; the global-directory kernel with two lanes per query is the fastest there (10 M: 0.25 ms
+// against 0.38 random).
+static SelectPlan select_plan(const bmx_ctx* ctx, const bmx_rs* rs, size_t q)
+{
+    if (rs->d_sel && ctx->rs_select_sel != 0) return {SELECT_SEL, 1, capped_grid(q, 512u, 256u * 8u), 256u, 0};
+    int lpq = ctx->rs_lanes ? ctx->rs_lanes : (q >= (1u << 16) ? RS_SELECT_LANES_DEFAULT : 8);
+    const bool top_ok = rs->d_stop && rs->d_sdir && ctx->rs_select_lines == 2 && ctx->rs_select_top != 0 &&
+                        (ctx->rs_select_top == 1 || (q >= (1u << 22) && !ctx->rs_sorted_hint)) && q < (1ull << 32) && ctx->max_lds_bytes >= STOP_BYTES + 16384u;
+    if (top_ok && !ctx->rs_lanes) lpq = 2;
+    if (ctx->rs_sorted_hint && !ctx->rs_lanes && q >= (1u << 16)) lpq = 2;
+    if (top_ok && lpq != 8) return {SELECT_TOP, lpq, capped_grid(q * (size_t)lpq, 1024u, 256u), 1024u, STOP_BYTES + 16u * 64u * 16u};
+    const SelectFamily f = lpq == 8 ? SELECT_TABLES : rs->d_sdir && ctx->rs_select_lines == 2 ? SELECT_SDIR
+                         : rs->d_lines && ctx->rs_select_lines ? SELECT_LINES : SELECT_TABLES;
+    return {f, lpq, capped_grid(q * (size_t)lpq, 256u, 256u * 16u), 256u, 0};
+}
+static int select_launch(bmx_ctx* ctx, const SelectPlan& pl, const bmx_vec* v, const bmx_rs* rs, const uint64_t* d_rank, size_t q,
+                         uint64_t* d_pos, uint8_t* d_found)
+{
+    const dim3 grid(pl.grid), wg(pl.wg);
+    const u64* r = (const u64*)d_rank; u64* pos = (u64*)d_pos; u8* found = (u8*)d_found;
+    if (pl.family == SELECT_SEL) {
+        auto fn = rs->sel_bits == 16 ? k_select_sel<u16> : k_select_sel<u32>;
+        hipLaunchKernelGGL(fn, grid, wg, pl.lds, ctx->stream, (const u8*)rs->d_sel, rs->count, r, (u64)q, pos, found);
+    } else if (pl.family == SELECT_TOP) {
+        auto fn = pl.lpq == 2 ? k_select_top<2> : k_select_top<4>;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+        hipLaunchKernelGGL(fn, grid, wg, pl.lds, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_stop, rs->stop_shift, rs->stop_fb, rs->count, r, (u64)q, pos, found);
+    } else if (pl.family == SELECT_SDIR) {
+        auto fn = pl.lpq == 2 ? k_select_sdir<2> : k_select_sdir<4>;
+        hipLaunchKernelGGL(fn, grid, wg, pl.lds, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_sdir, rs->sdir_shift, rs->count, r, (u64)q, pos, found);
+    } else if (pl.family == SELECT_LINES) {
+        auto fn = pl.lpq == 2 ? k_select_lines<2> : k_select_lines<4>;
+        hipLaunchKernelGGL(fn, grid, wg, pl.lds, ctx->stream, (const u32*)rs->d_lines, (const u16*)rs->d_dir8, v->nblocks, (const u64*)rs->d_rcount,
+                           (const u64*)rs->d_sample, rs->nsamples, rs->sample_shift, rs->count, r, (u64)q, pos, found);
+    } else {
+        auto fn = k_select;
+        if (pl.lpq == 2) fn = k_select_l<2>; else if (pl.lpq == 4) fn = k_select_l<4>;
+        hipLaunchKernelGGL(fn, grid, wg, pl.lds, ctx->stream, v->d_desc, v->nblocks, rs->d_rcount, rs->d_cum, rs->d_gidx, rs->d_sample, rs->nsamples,
+                           rs->sample_shift, rs->count, r, (u64)q, pos, found);
+    }
+    return BMX_OK;
+}
+
+// The host entries' round trip: one buffer for the queries and the answers (q x 16 bytes for rank, q x 17 for select: `found` set),
+// one upload, the device entry, the answers back, one synchronise; the buffer is given back before the error is mapped.
+static int rs_host_batch(bmx_ctx* ctx, const char* entry, const bmx_vec* v, const bmx_rs* rs, const uint64_t* in, size_t q,
+                         uint64_t* out, uint8_t* found)
+{
+    int rc = set_dev(ctx); if (rc) return rc;
+    if (!q) return BMX_OK;
+    DevBuf buf(ctx);
+    if ((rc = dmalloc(ctx, &buf.p, q * (found ? 17 : 16)))) return rc;
+    u64* d = (u64*)buf;
+    hipError_t e = hipMemcpyAsync(d, in, q * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        rc = found ? bmx_select_batch_dev(ctx, v, rs, d, q, d + q, (uint8_t*)(d + 2 * q)) : bmx_rank_batch_dev(ctx, v, rs, d, q, d + q);
+        if (!rc) e = hipMemcpyAsync(out, d + q, q * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (!rc && e == hipSuccess && found) e = hipMemcpyAsync(found, d + 2 * q, q, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    buf.reset();
+    if (e != hipSuccess) return fail_hip(e, entry, __LINE__);
+    return rc;
+}
+
+extern "C" {
 
 int bmx_rank_batch_dev(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uint64_t* d_n, size_t q, uint64_t* d_out)
 { ABI_TRY
     ARGCHK(ctx && v && rs && v->ctx == ctx && rs->ctx == ctx && rs->nblocks == v->nblocks && (q == 0 || (d_n && d_out)));
     int rc = set_dev(ctx); if (rc) return rc;
     if (!q) return BMX_OK;
-    // lanes per query (rs_lanes: 0 = automatic; batches too small to fill the chip keep the 8-lane kernel)
-    int lpq = ctx->rs_lanes ? ctx->rs_lanes : (q >= (1u << 16) ? RS_LANES_DEFAULT : 8);
-    u32 grid = (u32)std::min<size_t>((q * (size_t)lpq + 255) / 256, 256u * 16u);
-#define RANK_ARGS dim3(grid), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, \
-                  rs->d_rcount, rs->d_cum, rs->d_gidx, rs->count, (const u64*)d_n, (u64)q, (u64*)d_out
-    if (rs->d_lines && lpq != 8) {
-        if (lpq == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rank_lines<2>), dim3(grid), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, v->nblocks, rs->count, (const u64*)d_n, (u64)q, (u64*)d_out);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rank_lines<4>), dim3(grid), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, v->nblocks, rs->count, (const u64*)d_n, (u64)q, (u64*)d_out);
-    }
-    else if (lpq == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rank_l<2>), RANK_ARGS);
-    else if (lpq == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rank_l<4>), RANK_ARGS);
-    else hipLaunchKernelGGL(k_rank, RANK_ARGS);
-#undef RANK_ARGS
+    rank_launch(ctx, rank_plan(ctx, rs, q), v, rs, d_n, q, d_out);
     KCHK();
     return BMX_OK;
 ABI_END }
@@ -4236,56 +4410,7 @@ int bmx_select_batch_dev(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const
     ARGCHK(ctx && v && rs && v->ctx == ctx && rs->ctx == ctx && rs->nblocks == v->nblocks && (q == 0 || (d_rank && d_pos && d_found)));
     int rc = set_dev(ctx); if (rc) return rc;
     if (!q) return BMX_OK;
-    if (rs->d_sel && ctx->rs_select_sel != 0) {
-        // select lines: one lane and one 128-byte line per query, no search (bmx_kernels11.h); any batch size, any order
-        const u32 g = (u32)std::min<size_t>((q + 511) / 512, 256u * 8u);
-        if (rs->sel_bits == 16) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_sel<u16>), dim3(g), dim3(256), 0, ctx->stream, (const u8*)rs->d_sel, rs->count, (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_sel<u32>), dim3(g), dim3(256), 0, ctx->stream, (const u8*)rs->d_sel, rs->count, (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-        KCHK();
-        return BMX_OK;
-    }
-    int lpq = ctx->rs_lanes ? ctx->rs_lanes : (q >= (1u << 16) ? RS_SELECT_LANES_DEFAULT : 8);
-    // big batches over a vector whose directory summary fits LDS: k_select_top, two lanes per query (profiles/r05_select: 10 M random
-    // selects on configs[3] 0.377 ms against 0.416 / 0.436 for the global-directory kernel with four / two lanes, 100 M: 3.63 against
-    // 4.09; at 1 M the 129 KiB every workgroup copies first cost more than they save: 0.058 against 0.044 -- taken from 4 M queries)
-    const bool top_ok = rs->d_stop && rs->d_sdir && ctx->rs_select_lines == 2 && ctx->rs_select_top != 0 &&
-                        (ctx->rs_select_top == 1 || (q >= (1u << 22) && !ctx->rs_sorted_hint)) && q < (1ull << 32) && ctx->max_lds_bytes >= STOP_BYTES + 16384u;
-    if (top_ok && !ctx->rs_lanes) lpq = 2;
-    // ranks the caller says arrive in ascending order (cursor-style enumeration): neighbours share lines and directory entries;
-    // the global-directory kernel with two lanes per query is the fastest there (10 M: 0.25 ms against 0.38 random)
-    if (ctx->rs_sorted_hint && !ctx->rs_lanes && q >= (1u << 16)) lpq = 2;
-    u32 grid = (u32)std::min<size_t>((q * (size_t)lpq + 255) / 256, 256u * 16u);
-#define SEL_ARGS dim3(grid), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, \
-                 rs->d_rcount, rs->d_cum, rs->d_gidx, rs->d_sample, rs->nsamples, rs->sample_shift, rs->count, \
-                 (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found
-    const bool top = top_ok && lpq != 8;
-    if (top) {
-        // the directory's summary in LDS: one 1024-thread workgroup per CU (129 KiB of LDS each), one global read per query
-        const size_t lds = STOP_BYTES + 16u * 64u * 16u;                          // the summary + a queue of 64 parked queries per wave
-        auto fn = lpq == 2 ? k_select_top<2> : k_select_top<4>;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const u32 g = (u32)std::min<size_t>((q * (size_t)lpq + 1023) / 1024, 256u);
-        hipLaunchKernelGGL(fn, dim3(g), dim3(1024), lds, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_stop, rs->stop_shift, rs->stop_fb, rs->count,
-                           (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-    }
-    else if (rs->d_sdir && lpq != 8 && ctx->rs_select_lines == 2) {
-        if (lpq == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_sdir<2>), dim3(grid), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_sdir,
-                                         rs->sdir_shift, rs->count, (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_sdir<4>), dim3(grid), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u32*)rs->d_sdir,
-                                rs->sdir_shift, rs->count, (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-    }
-    else if (rs->d_lines && lpq != 8 && ctx->rs_select_lines) {
-        if (lpq == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_lines<2>), dim3(grid), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u16*)rs->d_dir8,
-                                         v->nblocks, (const u64*)rs->d_rcount, (const u64*)rs->d_sample, rs->nsamples, rs->sample_shift, rs->count,
-                                         (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_lines<4>), dim3(grid), dim3(256), 0, ctx->stream, (const u32*)rs->d_lines, (const u16*)rs->d_dir8,
-                                v->nblocks, (const u64*)rs->d_rcount, (const u64*)rs->d_sample, rs->nsamples, rs->sample_shift, rs->count,
-                                (const u64*)d_rank, (u64)q, (u64*)d_pos, (u8*)d_found);
-    }
-    else if (lpq == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_l<2>), SEL_ARGS);
-    else if (lpq == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_l<4>), SEL_ARGS);
-    else hipLaunchKernelGGL(k_select, SEL_ARGS);
-#undef SEL_ARGS
+    if ((rc = select_launch(ctx, select_plan(ctx, rs, q), v, rs, d_rank, q, d_pos, d_found))) return rc;   // (hipFuncSetAttribute, k_select_top only)
     KCHK();
     return BMX_OK;
 ABI_END }
@@ -4293,41 +4418,14 @@ ABI_END }
 int bmx_rank_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uint64_t* n, size_t q, uint64_t* out)
 { ABI_TRY
     ARGCHK(ctx && (q == 0 || (n && out)));
-    int rc = set_dev(ctx); if (rc) return rc;
-    if (!q) return BMX_OK;
-    DevBuf buf(ctx);
-    if ((rc = dmalloc(ctx, &buf.p, q * 16))) return rc;
-    u64* d = (u64*)buf;
-    hipError_t e = hipMemcpyAsync(d, n, q * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        rc = bmx_rank_batch_dev(ctx, v, rs, d, q, d + q);
-        if (!rc) e = hipMemcpyAsync(out, d + q, q * 8, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    buf.reset();
-    if (e != hipSuccess) return fail_hip(e, "bmx_rank_batch", __LINE__);
-    return rc;
+    return rs_host_batch(ctx, "bmx_rank_batch", v, rs, n, q, out, nullptr);
 ABI_END }
 
 int bmx_select_batch(bmx_ctx* ctx, const bmx_vec* v, const bmx_rs* rs, const uint64_t* rank, size_t q,
                      uint64_t* pos, uint8_t* found)
 { ABI_TRY
     ARGCHK(ctx && (q == 0 || (rank && pos && found)));
-    int rc = set_dev(ctx); if (rc) return rc;
-    if (!q) return BMX_OK;
-    DevBuf buf(ctx);
-    if ((rc = dmalloc(ctx, &buf.p, q * 17))) return rc;
-    u64* d = (u64*)buf;
-    hipError_t e = hipMemcpyAsync(d, rank, q * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        rc = bmx_select_batch_dev(ctx, v, rs, d, q, d + q, (uint8_t*)(d + 2 * q));
-        if (!rc) e = hipMemcpyAsync(pos, d + q, q * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpyAsync(found, d + 2 * q, q, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    buf.reset();
-    if (e != hipSuccess) return fail_hip(e, "bmx_select_batch", __LINE__);
-    return rc;
+    return rs_host_batch(ctx, "bmx_select_batch", v, rs, rank, q, pos, found);
 ABI_END }
 
 } // extern "C"
@@ -4353,13 +4451,8 @@ static int rankc_run(bmx_ctx* ctx, int dir, const bmx_vec* idx, const bmx_rs* rs
     const u64* P = nullptr; uint64_t total = 0;
     if (rs) { P = rs->d_rcount; total = rs->count; }
     else if (inb) {
-        if ((rc = dmalloc(ctx, &d_bc.p, (size_t)inb * 4)) || (rc = dmalloc(ctx, &d_rc.p, (size_t)inb * 8))) return rc;
-        hipLaunchKernelGGL(k_block_counts, dim3((inb + 3) / 4), dim3(256), 0, ctx->stream, (const u64*)idx->d_desc, inb, (u32*)d_bc);
-        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)d_bc, inb, (u64*)d_rc, ctx->d_small);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        P = (const u64*)d_rc.p; total = ctx->h_small[0];
+        if ((rc = running_counts(ctx, idx, d_bc, d_rc, &total))) return rc;
+        P = (const u64*)d_rc.p;
         d_bc.reset();
     }
     const uint64_t nbits_out = dir == 0 ? total : idx->nbits;

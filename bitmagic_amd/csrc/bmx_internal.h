@@ -117,13 +117,13 @@ struct bmx_ctx {
     int eq_big_shape = 2;      // lean table: 2 = 768 threads at 3 waves per SIMD, 8 filter reads in flight, 256 Kbit filter, 512-entry queues -- taken for every batch size over more than 16 planes; 1 = 512 threads, 2 waves per SIMD; 0 = 128 Kbit filter + 1,024-entry queues
     int eq_big = -1;           // batched equality counts: -1 = lean 9,216-value table when the batch has more than 2,048 values, 0 = never, 1 = always
     int coll_window = 0;       // block columns per launch of k_coll_apply (0 = one launch)
-    int rs_lines = 1;          // build_rs_index also lays the vector out as rank lines (one 128-B line per rank query; +108 % of the raw bits): 1 = where that is <= 1.2 x the vector's own device bytes (dense vectors), 2 = always, 0 = never
+    int rs_lines = 1;          // build_rs_index also lays the vector out as rank lines (one 128-B line per rank query; +108 % of the raw bits): 1 = where that is <= 2 x the vector's own device bytes (bit-blocks in more than about half of its block columns), 2 = always, 0 = never
     int rs_sdir_shift = 0;     // ones per select-directory entry = 2^this; 0 = from the density (an entry per ~10 lines); grown when the directory would pass 8 MB
-    int rs_select_lines = 2;   // select through the rank lines (octant directory + interpolated line guess verified by the line headers): 0 = k_select_l, 2 = select directory over the lines (k_select_sdir)
+    int rs_select_lines = 2;   // select through the rank lines (octant directory + interpolated line guess verified by the line headers): 0 = k_select_l, 1 = k_select_lines, 2 = select directory over the lines (k_select_sdir)
     int rs_select_top = -1;    // select with the 65,536-entry directory summary in LDS (k_select_top): -1 = batches of >= 4 M queries, 0 = never, 1 = always (where the summary exists)
     int rs_select_sel = -1;    // select lines (k_select_sel: the ones' positions laid out 60 / 30 per 128-byte line, one line per query, no search): -1 = built where they cost <= 2 x the vector + its rank lines, 0 = never built / never used, 1 = always (16-bit offsets, 32-bit if a line spans >= 2^16 bits), 2 = always with 32-bit offsets
     int rs_sorted_hint = 0;    // the caller's select batches arrive with ascending ranks (enumeration): the shape that is fastest for them
-    int rs_lanes = 0;          // rank: lanes per query (k_rank_l): 0 = automatic, 8 = the original kernel, 2, 4
+    int rs_lanes = 0;          // rank and select: lanes per query: 0 = automatic (rank_plan / select_plan, bmx.hip), 8 = the original kernels (k_rank / k_select, tables only), 2, 4
     int rankc_path = -1;       // rank_compressor (bmx_kernels15.h): -1 = automatic, 0 = ascending positions into the sorted path of from_indices, 1 = whole blocks
     int xcd_swz = 1;
 };

@@ -1511,6 +1511,68 @@ def test_range_hint(ctx, port, agg_path):
         agg.reset_range_hint()
 
 
+def _rs_mixed_words(rng, nblk=23):
+    """-> (nbits, words): nblk blocks of every kind in turn -- NULL, FULL, bit, sparse GAP, GAP of few wide runs, GAP of many short
+    runs -- cut 777 bits short of the last block border"""
+    nbits = nblk * 65536 - 777
+    words = np.zeros(nblk * 2048, np.uint32)
+    for nb in range(nblk):
+        kind = nb % 6
+        if kind == 0: continue                                            # NULL
+        lo = nb * 2048
+        if kind == 1: words[lo:lo + 2048] = 0xFFFFFFFF                   # FULL
+        elif kind == 2: words[lo:lo + 2048] = rng.integers(0, 1 << 32, 2048, dtype=np.uint64).astype(np.uint32)   # bit
+        elif kind == 3:                                                   # sparse GAP
+            for b in rng.integers(0, 65536, 40): words[lo + (b >> 5)] |= np.uint32(1 << (b & 31))
+        elif kind == 4:                                                   # long runs (GAP with few, wide runs)
+            words[lo + 100:lo + 900] = 0xFFFFFFFF; words[lo + 1500:lo + 1600] = 0xFFFFFFFF
+        else:                                                             # many short runs: still GAP (< 1276 runs)
+            for b in rng.integers(0, 65536, 500): words[lo + (b >> 5)] |= np.uint32(1 << (b & 31))
+    last_bits = nbits - (nblk - 1) * 65536
+    tail = np.unpackbits(words[(nblk - 1) * 2048:].view(np.uint8), bitorder="little"); tail[last_bits:] = 0
+    words[(nblk - 1) * 2048:] = np.packbits(tail, bitorder="little").view(np.uint32)
+    return nbits, words
+
+
+def _ones_of(words, nbits):
+    """the positions of the set bits, ascending: the NumPy reference of rank and select (read-only: shared between tests)"""
+    ones = np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")[:nbits]).astype(np.uint64)
+    ones.setflags(write=False)
+    return ones
+
+
+def _check_rank_np(v, rs, ones, q, what):
+    assert (v.rank(q, rs) == np.searchsorted(ones, q, "right").astype(np.uint64)).all(), what
+
+
+def _check_select_np(v, rs, ones, r, what):
+    found, pos = v.select(r, rs)
+    live = (r >= 1) & (r <= ones.size)
+    exp = np.zeros(r.size, np.uint64)
+    exp[live] = ones[(r[live] - np.uint64(1)).astype(np.int64)]
+    assert (found == live).all() and (pos == exp).all(), what              # (pos == 0 where not found)
+
+
+def _check_against_oracle(v, rs, prs, q, r):
+    """the same queries against the reference's own rs_index: ties the NumPy rule above to it"""
+    assert (v.rank(q, rs) == prs.rank(q)).all()
+    found, pos = v.select(r, rs)
+    ppos, pfound = prs.select(r)
+    assert (found == pfound).all() and (pos[found] == ppos[pfound]).all() and (pos[~found] == 0).all()
+
+
+_RS_MIXED = []
+
+
+def _rs_mixed_reference():
+    """(nbits, words, ones) of one 23-block vector of every block kind, computed once"""
+    if not _RS_MIXED:
+        nbits, words = _rs_mixed_words(np.random.default_rng(4242))
+        words.setflags(write=False)
+        _RS_MIXED.append((nbits, words, _ones_of(words, nbits)))
+    return _RS_MIXED[0]
+
+
 @pytest.mark.parametrize("unroll,lines,sel,selfmt", [(8, 0, 0, 0), (2, 0, 0, 0), (4, 0, 0, 0), (2, 1, 1, 0), (4, 1, 1, 0), (2, 1, 2, 0), (4, 1, 2, 0), (4, 1, (2, 6), 0), (4, 1, (2, 16), 0),
                                                      (4, 1, (2, 0, 1), 0), (2, 1, (2, 6, 1), 0), (4, 1, (2, 16, 1), 0),
                                                      (2, 1, 2, 1), (8, 0, 0, 1), (2, 1, 2, 2), (2, 0, 0, -1)])
@@ -1535,25 +1597,7 @@ def test_rank_select_queries_in_flight_forms(port, unroll, lines, sel, selfmt):
     # take the 32-bit form; 2 = 32-bit offsets asked for; -1 = the memory policy decides
     c.set_tuning("rs_select_sel", selfmt)
     rng = np.random.default_rng(1234 + unroll)
-    nblk = 23
-    nbits = nblk * 65536 - 777
-    p = port.new(nbits)
-    words = np.zeros(nblk * 2048, np.uint32)
-    for nb in range(nblk):
-        kind = nb % 6
-        if kind == 0: continue                                            # NULL
-        lo = nb * 2048
-        if kind == 1: words[lo:lo + 2048] = 0xFFFFFFFF                   # FULL
-        elif kind == 2: words[lo:lo + 2048] = rng.integers(0, 1 << 32, 2048, dtype=np.uint64).astype(np.uint32)   # bit
-        elif kind == 3:                                                   # sparse GAP
-            for b in rng.integers(0, 65536, 40): words[lo + (b >> 5)] |= np.uint32(1 << (b & 31))
-        elif kind == 4:                                                   # long runs (GAP with few, wide runs)
-            words[lo + 100:lo + 900] = 0xFFFFFFFF; words[lo + 1500:lo + 1600] = 0xFFFFFFFF
-        else:                                                             # many short runs: still GAP (< 1276 runs)
-            for b in rng.integers(0, 65536, 500): words[lo + (b >> 5)] |= np.uint32(1 << (b & 31))
-    last_bits = nbits - (nblk - 1) * 65536
-    tail = np.unpackbits(words[(nblk - 1) * 2048:].view(np.uint8), bitorder="little"); tail[last_bits:] = 0
-    words[(nblk - 1) * 2048:] = np.packbits(tail, bitorder="little").view(np.uint32)
+    nbits, words = _rs_mixed_words(rng)
     p = port.import_words(words, True, nbits)
     assert set(p.flatten()[0].tolist()) == {0, 1, 2, 3}
     v = bm.bvector.from_block_table(c, nbits, *p.flatten())
@@ -1576,6 +1620,88 @@ def test_rank_select_queries_in_flight_forms(port, unroll, lines, sel, selfmt):
     found, pos = v.select(allr, rs)
     ppos, pfound = prs.select(allr)
     assert found.all() and (pos == ppos).all()
+    del rs, v
+    c.close()
+
+
+@pytest.mark.parametrize("lines,selfmt", [(0, 0), (2, 0), (2, 1)])
+def test_rank_select_automatic_choice(port, lines, selfmt):
+    """rs_lanes 0: the library picks the lanes per query and the kernel from the batch size, the index and rs_sorted_hint.  Batches of
+    65,535 and 65,536 queries (the threshold of the automatic lanes) over an index of tables only, one with rank lines and select
+    directory, and one with select lines too; each with the sorted hint off and on (hinted batches are sorted as a whole, so their dead
+    queries stand where ascending order puts them) and one hinted batch that is not ascending: the hint may cost time, never answers.
+    Over the rank lines also 2^22 - 1 and 2^22 random ranks with rs_select_top -1: the threshold of k_select_top.  Every batch holds
+    the dead queries (rank 0, count + 1, 2^40; positions nbits and nbits + 70000), unhinted ones at their end.  Expected values come
+    from NumPy over the words; a few hundred queries of each kind also go against the oracle."""
+    nbits, words, ones = _rs_mixed_reference()
+    cnt = ones.size
+    c = bm.context(0)
+    for k, x in (("rs_lanes", 0), ("rs_lines", lines), ("rs_select_sel", selfmt), ("rs_select_top", -1)): c.set_tuning(k, x)
+    p = port.import_words(np.array(words), True, nbits)
+    assert p.count() == cnt
+    v = bm.bvector.from_block_table(c, nbits, *p.flatten())
+    rs = v.build_rs_index()
+    info = rs.info()
+    assert info["has_lines"] == bool(lines) and info["select_offset_bits"] == (32 if selfmt else 0)
+    rng = np.random.default_rng(99 + lines + selfmt)
+    dead_q, dead_r = np.array([nbits, nbits + 70000], np.uint64), np.array([0, cnt + 1, 2 ** 40], np.uint64)
+
+    def batches(nq, hint):
+        q = np.concatenate([rng.integers(0, nbits, size=nq - dead_q.size).astype(np.uint64), dead_q])
+        r = np.concatenate([rng.integers(1, cnt + 1, size=nq - dead_r.size).astype(np.uint64), dead_r])
+        return (np.sort(q), np.sort(r)) if hint else (q, r)
+
+    for nq in (65535, 65536):
+        for hint in (0, 1):
+            c.set_tuning("rs_sorted_hint", hint)
+            q, r = batches(nq, hint)
+            assert q.size == nq and r.size == nq
+            _check_rank_np(v, rs, ones, q, (nq, hint))
+            _check_select_np(v, rs, ones, r, (nq, hint))
+    c.set_tuning("rs_sorted_hint", 1)
+    q, r = batches(65536, 0)                                               # hinted, not ascending
+    _check_rank_np(v, rs, ones, q, "hinted, unsorted")
+    _check_select_np(v, rs, ones, r, "hinted, unsorted")
+    c.set_tuning("rs_sorted_hint", 0)
+    if lines and not selfmt:
+        for nq in ((1 << 22) - 1, 1 << 22):
+            _check_select_np(v, rs, ones, batches(nq, 0)[1], nq)
+    q, r = batches(300, 0)
+    _check_against_oracle(v, rs, port.rs_build(p), q, r)
+    del rs, v
+    c.close()
+
+
+def test_select_summary_dropped_when_groups_spread(port):
+    """2,000 GAP blocks of three ones each: a select-directory entry covers 2^6 = 64 ones, a group of 64 summary entries 4,096 ones =
+    1,365 blocks x 69 lines, more than the 65,000 lines a group may span even in whole lines (fb = 0).  bmx_rs_build must drop the
+    directory's summary (k_select_top) although rs_select_top 1 asks for it, and select answers through the directory: the index's
+    bytes are its tables, rank lines, octant directory and select directory, without the 135,168 bytes of a summary."""
+    nblk, offs = 2000, np.array([5, 30000, 65000], np.int64)
+    nbits = nblk * 65536
+    words = np.zeros(nblk * 2048, np.uint32)
+    for o in offs: words[np.arange(nblk) * 2048 + (o >> 5)] |= np.uint32(1 << (o & 31))
+    ones = _ones_of(words, nbits)
+    cnt = ones.size
+    assert cnt == 3 * nblk
+    c = bm.context(0)
+    for k, x in (("rs_lines", 2), ("rs_select_sel", 0), ("rs_select_top", 1), ("rs_sdir_shift", 0)): c.set_tuning(k, x)
+    p = port.import_words(words, True, nbits)
+    assert set(p.flatten()[0].tolist()) == {3}                            # GAP blocks only
+    v =bm.bvector.from_block_table(c, nbits, *p.flatten())
+    rs = v.build_rs_index()
+    sdir_entries = ((cnt + 63) >> 6) + 1
+    assert rs.info() == {"bytes": nblk * (4 + 8 + 8 + 2 * 128) + nblk * 69 * 128 + nblk * 16 + sdir_entries * 4, "has_lines": True,
+                         "select_offset_bits": 0, "select_lines_bytes": 0}
+    rng = np.random.default_rng(7)
+    dead_r = np.array([0, cnt + 1, 2 ** 40], np.uint64)
+    _check_select_np(v, rs, ones, np.arange(1, cnt + 1, dtype=np.uint64), "in order")
+    r = np.concatenate([rng.integers(1, cnt + 1, size=1000).astype(np.uint64), dead_r])
+    _check_select_np(v, rs, ones, r, "random")
+    _check_rank_np(v, rs, ones, ones, "at every one")
+    _check_rank_np(v, rs, ones, ones + np.uint64(1), "behind every one")
+    q = np.concatenate([rng.choice(ones, 98), rng.choice(ones, 98) + np.uint64(1), np.array([0, nbits - 1, nbits, nbits + 70000], np.uint64)])
+    _check_against_oracle(v, rs, port.rs_build(p), q, r[-200:])
     del rs, v
     c.close()
 
