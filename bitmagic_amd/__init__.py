@@ -949,6 +949,49 @@ class aggregator:
         """asynchronous run; counts land in device memory (e.g. a torch tensor's data_ptr())"""
         check(lib().bmx_pipeline_run_counts_dev(self.ctx._h, pipe._h, nb_from, nb_to, C.c_void_p(d_counts_ptr)))
 
+    def combine_and_sub_indices(self, pipe: pipeline, nb_from: int = 0, nb_to: int = ID_MAX, width: int = 8):
+        """-> (offsets, ids): the hits of EVERY arg-group as ascending positions, all groups in one CSR -- ids[offsets[g]:
+        offsets[g + 1]] is what combine_and_sub(bi, and_g, n, sub_g, m) (:1226-1284) feeds its iterator for group g, restricted to
+        block columns [nb_from, nb_to) (positions stay absolute).  One device run for the batch (bmx_pipeline_run_indices);
+        the search count limit does not apply."""
+        if not pipe.is_complete():
+            raise RuntimeError("pipeline is not complete()")
+        offsets = np.zeros(pipe.size() + 1, np.uint64)
+        op = offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+        dt = np.uint64 if width == 8 else np.uint32
+        n = C.c_uint64()
+        # the capacity protocol of bmx_vec_to_indices: a call into a buffer of the size the pipeline's last run needed (65,536
+        # entries the first time); when that is too small nothing but the total and the offsets was written, and a second call
+        # writes into a buffer of that size
+        cap = max(getattr(pipe, "_hits_hint", 0), 65536)
+        ids = np.empty(cap, dt)
+        rc = lib().bmx_pipeline_run_indices(self.ctx._h, pipe._h, nb_from, nb_to, width, op, _ptr(ids), cap, C.byref(n))
+        if rc == _ffi.ERR_RANGE and n.value > cap:
+            ids = np.empty(n.value, dt)
+            rc = lib().bmx_pipeline_run_indices(self.ctx._h, pipe._h, nb_from, nb_to, width, op, _ptr(ids), n.value, C.byref(n))
+        check(rc)
+        pipe._hits_hint = int(n.value)
+        return offsets, ids[:n.value]
+
+    def combine_and_sub_indices_dev(self, pipe: pipeline, d_out_ptr: int, cap: int, nb_from: int = 0, nb_to: int = ID_MAX,
+                                    width: int = 8, d_offsets_ptr: int = 0):
+        """-> (offsets, n).  The positions land in device memory of `cap` entries (e.g. a torch tensor's data_ptr()), complete on
+        the context's stream; d_offsets_ptr (optional): device memory for the size() + 1 offsets.  n > cap raises BmxError
+        (ERR_RANGE) with nothing written; e.n then holds the number needed and e.offsets the segments."""
+        if not pipe.is_complete():
+            raise RuntimeError("pipeline is not complete()")
+        offsets = np.zeros(pipe.size() + 1, np.uint64)
+        n = C.c_uint64()
+        rc = lib().bmx_pipeline_run_indices_dev(self.ctx._h, pipe._h, nb_from, nb_to, width, offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                C.c_void_p(d_offsets_ptr or None), C.c_void_p(d_out_ptr or None), int(cap), C.byref(n))
+        if rc != _ffi.OK:
+            try:
+                check(rc)
+            except BmxError as e:
+                e.n, e.offsets = int(n.value), offsets
+                raise
+        return offsets, int(n.value)
+
 
 CMP_GT, CMP_GE, CMP_LT, CMP_LE, CMP_RANGE, CMP_EQ, CMP_ZERO, CMP_NONZERO = range(8)
 
@@ -1086,10 +1129,39 @@ class slice_scanner:
             return None, False
         return self.agg.combine_and_sub(g[0], g[1])
 
-    def find_eq_indices(self, value: int) -> np.ndarray:
-        """find_eq(sv, value, BII)  src/bmsparsevec_algo.h:1096: matching rows as sorted indices"""
+    def find_eq_indices(self, value):
+        """find_eq(sv, value, BII)  src/bmsparsevec_algo.h:1096: matching rows as sorted indices.  A sequence of values is a
+        batch: -> (offsets, ids), ids[offsets[q]:offsets[q + 1]] = the rows equal to values[q] -- one AND-SUB group per value in
+        ONE index-list pipeline run (aggregator.combine_and_sub_indices); a value with a set bit that has no plane gives an empty
+        segment; value 0 goes through the comparison kernel and is spliced in on the host"""
+        if np.ndim(value) > 0:
+            return self._find_eq_indices_batch([int(v) for v in value])
         t, found = self.find_eq(value)
         return t.to_indices() if (found and t is not None) else np.zeros(0, np.uint64)
+
+    def _find_eq_indices_batch(self, vals):
+        pipe = pipeline(self.ctx, agg_opt_disable_bvects_and_counts)
+        slot = []
+        for v in vals:
+            g = self._groups(v) if v else None
+            if g is None:
+                slot.append(-1); continue
+            ag = pipe.add()
+            for x in g[0]: ag.add(x, 0)
+            for x in g[1]: ag.add(x, 1)
+            slot.append(pipe.size() - 1)
+        poff, pids = np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        if pipe.size():
+            pipe.complete()
+            poff, pids = self.agg.combine_and_sub_indices(pipe)
+        if pipe.size() == len(vals):
+            return poff, pids                                            # every value has its own group: no splice
+        zero = self._compare(CMP_EQ, 0).to_indices() if 0 in vals else None
+        empty = np.zeros(0, np.uint64)
+        parts = [zero if v == 0 else (pids[int(poff[s]):int(poff[s + 1])] if s >= 0 else empty) for v, s in zip(vals, slot)]
+        offsets = np.zeros(len(vals) + 1, np.uint64)
+        offsets[1:] = np.cumsum([p.size for p in parts], dtype=np.uint64)
+        return offsets, (np.concatenate(parts) if parts else empty)
 
     def find_first_eq(self, value: int):
         g = self._groups(int(value))

@@ -105,6 +105,8 @@ def lib() -> C.CDLL:
         "bmx_pipeline_last_window_groups": (i32, [vp, P(u32), u32, P(u32)]),
         "bmx_pipeline_run_counts": (i32, [vp, vp, u32, u32, P(u64)]),
         "bmx_pipeline_run_counts_dev": (i32, [vp, vp, u32, u32, vp]),
+        "bmx_pipeline_run_indices": (i32, [vp, vp, u32, u32, i32, P(u64), vp, u64, P(u64)]),
+        "bmx_pipeline_run_indices_dev": (i32, [vp, vp, u32, u32, i32, P(u64), vp, vp, u64, P(u64)]),
         "bmx_pipeline_run_results": (i32, [vp, vp, P(vp), P(u64), vp, P(vp)]),
         "bmx_pipeline_run_results_range": (i32, [vp, vp, u32, u32, P(vp), P(u64), vp, P(vp)]),
         "bmx_pipeline_run_results_hint": (i32, [vp, vp, u64, u64, P(vp), P(u64), vp, P(vp)]),

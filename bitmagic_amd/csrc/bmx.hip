@@ -18,6 +18,7 @@
 #include "bmx_kernels13.h"
 #include "bmx_kernels14.h"
 #include "bmx_kernels15.h"
+#include "bmx_kernels16.h"
 
 #include <algorithm>
 #include <atomic>
@@ -910,6 +911,7 @@ static int ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
     else if (k == "rs_select_top") { ARGCHK(value >= -1 && value <= 1); ctx->rs_select_top = value; }
     else if (k == "rs_lanes") { ARGCHK(value == 0 || value == 2 || value == 4 || value == 8); ctx->rs_lanes = value; }
     else if (k == "pipe_wg") { ARGCHK(value == 0 || (value >= 64 && value <= 1024 && value % 64 == 0)); ctx->pipe_wg = value; }
+    else if (k == "hits_table_kb") { ARGCHK(value >= 0 && value <= (4 << 20)); ctx->hits_table_kb = value; }
     else if (k == "rankc_path") { ARGCHK(value >= -1 && value <= 1); ctx->rankc_path = value; }
     else if (k == "xcd_swizzle") ctx->xcd_swz = value != 0;
     else { g_last_error = "unknown tuning key"; return BMX_ERR_BADARG; }
@@ -1056,7 +1058,7 @@ int bmx_ctx_create(int device, void* stream, bmx_ctx** out)
     // an invalid value is ignored (the default stays)
     static const char* const env_keys[][2] = {
         {"BMX_PIPE_UNROLL", "pipe_unroll"}, {"BMX_PIPE_ROWS", "pipe_rows"}, {"BMX_PIPE_NT", "pipe_nt"},
-        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}};
+        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}, {"BMX_HITS_TABLE_KB", "hits_table_kb"}};
     for (auto& kv : env_keys)
         if (const char* e = getenv(kv[0])) (void)ctx_set_tuning(ctx.get(), kv[1], atoi(e));
     g_last_error.clear();
@@ -2641,6 +2643,134 @@ int bmx_pipeline_run_counts(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
         if (e != hipSuccess) rc = fail_hip(e, "counts readback", __LINE__);
     }
     return rc;
+ABI_END }
+
+} // extern "C"
+
+// ---- every arg-group's hits as one CSR of ascending positions (bmx_kernels16.h) ----
+// The (column, group) hit table takes 12 B per item (u32 ones + u64 start position): the arg-groups are processed in CHUNKS whose
+// table stays within hits_table_kb and whose item count stays within the 32-bit item space of the kernels; a chunk is at least one
+// group.  One chunk: the totals come from k_pipe_hit_counts itself.  More: the per-group totals come first from the ordinary
+// counts run (no limit, same column range), then every chunk is counted, scanned and emitted in turn.
+struct HitsPlan { u32 ncw, per_chunk, nchunks, unroll; };
+static HitsPlan hits_plan(const bmx_ctx* ctx, const bmx_pipeline* p, u32 nb_from, u32 nb_to)
+{
+    HitsPlan pl{};
+    pl.ncw = nb_to - nb_from;
+    const u64 budget_items = (u64)ctx->hits_table_kb * 1024u / 12u;
+    const u64 cap_items = std::min<u64>(budget_items, 0xFFFFFFF0ull);
+    pl.per_chunk = (u32)std::min<u64>(std::max<u64>(cap_items / std::max(pl.ncw, 1u), 1u), std::max(p->ngroups, 1u));
+    pl.nchunks = (p->ngroups + pl.per_chunk - 1u) / pl.per_chunk;
+    pl.unroll = ctx->pipe_unroll == 1 ? 1u : ctx->pipe_unroll == 2 ? 2u : 4u;       // as the general counts kernel (counts_plan)
+    return pl;
+}
+
+typedef void (*hit_counts_fn)(const u64*, const u32*, const u32*, const u32*, u32, u32, u32, u32, u32, int, u32*);
+template <typename T> using hit_emit_fn = void (*)(const u64*, const u32*, const u32*, const u32*, u32, u32, u32, u32, u32, int,
+                                                   const u32*, const u64*, const u64*, T*, u64);
+static hit_counts_fn hit_counts_kernel(u32 unroll) { return unroll == 1 ? k_pipe_hit_counts<1> : unroll == 2 ? k_pipe_hit_counts<2> : k_pipe_hit_counts<4>; }
+template <typename T>
+static hit_emit_fn<T> hit_emit_kernel(u32 unroll) { return unroll == 1 ? k_pipe_hit_emit<1, T> : unroll == 2 ? k_pipe_hit_emit<2, T> : k_pipe_hit_emit<4, T>; }
+
+// one run: the plan, the column range and the hit table (ones | start positions) every chunk re-uses
+struct HitsRun {
+    bmx_ctx* ctx; const bmx_pipeline* p; HitsPlan pl; u32 nb_from;
+    u32* d_cnt; u64* d_start;
+    // the launch of the item kernels over the chunk of groups [g0, g0 + ng): (<= 0xFFFFFFF0 items by the plan; one group: ncw itself)
+    u32 nitems(u32 ng) const { return pl.ncw * ng; }
+    dim3 grid(u32 ng) const { return dim3((nitems(ng) + 3u) / 4u); }
+    const u32* row_off(u32 g0) const { return p->d_meta + g0; }
+    const u32* and_n(u32 g0) const { return p->d_meta + p->ngroups + g0; }
+    const u32* sub_n(u32 g0) const { return p->d_meta + 2 * (size_t)p->ngroups + g0; }
+};
+static const size_t HITS_LDS = 4 * 2048 * 4;                   // 8 KiB per wave, as k_pipe_counts
+
+// the chunk's table: ones of every item, their start positions inside the group and (d_tot != null) the totals of its groups
+static int hits_count(const HitsRun& r, u32 g0, u32 ng, u64* d_tot)
+{
+    bmx_ctx* ctx = r.ctx;
+    HIPCHK(hipMemsetAsync(r.d_cnt, 0, (size_t)r.nitems(ng) * 4, ctx->stream));
+    hipLaunchKernelGGL(hit_counts_kernel(r.pl.unroll), r.grid(ng), dim3(256), HITS_LDS, ctx->stream, (const u64*)r.p->d_dmat, r.row_off(g0), r.and_n(g0),
+                       r.sub_n(g0), r.p->col_stride, ng, r.nb_from, r.pl.ncw, r.nitems(ng), ctx->xcd_swz, r.d_cnt);
+    KCHK();
+    hipLaunchKernelGGL(k_pipe_hit_scan, dim3(ng), dim3(256), 0, ctx->stream, (const u32*)r.d_cnt, r.pl.ncw, r.d_start, d_tot);
+    KCHK();
+    return BMX_OK;
+}
+// the chunk's positions from its table, into d_out (`total` entries) at the CSR offsets d_off (of the whole pipeline)
+template <typename T>
+static int hits_emit(const HitsRun& r, u32 g0, u32 ng, const u64* d_off, void* d_out, u64 total)
+{
+    bmx_ctx* ctx = r.ctx;
+    hipLaunchKernelGGL(hit_emit_kernel<T>(r.pl.unroll), r.grid(ng), dim3(256), HITS_LDS, ctx->stream, (const u64*)r.p->d_dmat, r.row_off(g0), r.and_n(g0),
+                       r.sub_n(g0), r.p->col_stride, ng, r.nb_from, r.pl.ncw, r.nitems(ng), ctx->xcd_swz, (const u32*)r.d_cnt, (const u64*)r.d_start,
+                       d_off + g0, (T*)d_out, total);
+    KCHK();
+    return BMX_OK;
+}
+
+static int pipe_indices_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, int width, uint64_t* offsets,
+                             uint64_t* d_offsets, void* out, bool out_is_host, uint64_t cap, uint64_t* n)
+{
+    ARGCHK(ctx && p && p->ctx == ctx && n && (width == 4 || width == 8) && (cap == 0 || out) && (offsets || !out_is_host));
+    int rc = set_dev(ctx); if (rc) return rc;
+    *n = 0;
+    if ((rc = pipe_range(p, nb_from, nb_to))) return rc;
+    if (width == 4 && (uint64_t)p->ncols > 65536ull) { g_last_error = "32-bit positions cannot address this pipeline's vectors: use width 8"; return BMX_ERR_RANGE; }
+    const u32 ng = p->ngroups;
+    const HitsPlan pl = hits_plan(ctx, p, nb_from, nb_to);
+    if (!ng || !pl.ncw) {
+        if (offsets) for (u32 g = 0; g <= ng; ++g) offsets[g] = 0;
+        if (d_offsets) HIPCHK(hipMemsetAsync(d_offsets, 0, ((size_t)ng + 1) * 8, ctx->stream));
+        return BMX_OK;
+    }
+    // group totals (ng) | offsets (ng + 1; not used when the caller gave device memory for them);  start positions (u64) | ones (u32)
+    const size_t tab_items = (size_t)pl.per_chunk * pl.ncw;
+    DevBuf d_tab(ctx), d_tot_off(ctx), host_out(ctx);
+    if ((rc = dmalloc(ctx, &d_tot_off.p, ((size_t)ng * 2 + 1) * 8)) || (rc = dmalloc(ctx, &d_tab.p, tab_items * 12))) return rc;
+    u64* d_tot = (u64*)d_tot_off; u64* d_off = d_offsets ? d_offsets : d_tot + ng;
+    const HitsRun run{ctx, p, pl, nb_from, (u32*)((u64*)d_tab + tab_items), (u64*)d_tab};
+    if (pl.nchunks > 1) rc = pipeline_run_counts_impl(ctx, p, nb_from, nb_to, d_tot, false);
+    else rc = hits_count(run, 0u, ng, d_tot);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pipe_hit_offsets, dim3(1), dim3(256), 0, ctx->stream, (const u64*)d_tot, ng, d_off, ctx->d_small);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (offsets) HIPCHK(hipMemcpyAsync(offsets, d_off, ((size_t)ng + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    const uint64_t total = ctx->h_small[0];
+    *n = total;
+    if (total > cap) { g_last_error = "output buffer too small for the positions (n holds the number needed, offsets the segments)"; return BMX_ERR_RANGE; }
+    if (!total) return BMX_OK;
+    const size_t bytes = (size_t)total * (size_t)width;
+    if (out_is_host && (rc = dmalloc(ctx, &host_out.p, bytes))) return rc;
+    void* d_out = out_is_host ? host_out.p : out;
+    auto emit = [&](u32 g0, u32 cg) { return width == 8 ? hits_emit<u64>(run, g0, cg, d_off, d_out, total) : hits_emit<u32>(run, g0, cg, d_off, d_out, total); };
+    if (pl.nchunks == 1) rc = emit(0u, ng);                   // (its table is the one the totals came from)
+    else for (u32 g0 = 0; g0 < ng && !rc; g0 += pl.per_chunk) {
+        const u32 cg = std::min(pl.per_chunk, ng - g0);
+        if (!(rc = hits_count(run, g0, cg, nullptr))) rc = emit(g0, cg);
+    }
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (out_is_host) {
+        HIPCHK(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    return BMX_OK;
+}
+
+extern "C" {
+
+int bmx_pipeline_run_indices(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, int width, uint64_t* offsets,
+                             void* out, uint64_t cap, uint64_t* n)
+{ ABI_TRY
+    return pipe_indices_impl(ctx, p, nb_from, nb_to, width, offsets, nullptr, out, true, cap, n);
+ABI_END }
+
+int bmx_pipeline_run_indices_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, int width, uint64_t* offsets,
+                                 uint64_t* d_offsets, void* d_out, uint64_t cap, uint64_t* n)
+{ ABI_TRY
+    return pipe_indices_impl(ctx, p, nb_from, nb_to, width, offsets, d_offsets, d_out, false, cap, n);
 ABI_END }
 
 int bmx_pipeline_operand_bytes(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, uint64_t* bytes)

@@ -125,6 +125,7 @@ struct bmx_ctx {
     int rs_sorted_hint = 0;    // the caller's select batches arrive with ascending ranks (enumeration): the shape that is fastest for them
     int rs_lanes = 0;          // rank and select: lanes per query: 0 = automatic (rank_plan / select_plan, bmx.hip), 8 = the original kernels (k_rank / k_select, tables only), 2, 4
     int rankc_path = -1;       // rank_compressor (bmx_kernels15.h): -1 = automatic, 0 = ascending positions into the sorted path of from_indices, 1 = whole blocks
+    int hits_table_kb = 512 * 1024;   // bmx_pipeline_run_indices: KiB of the (column, group) hit table (12 B per item) one chunk of arg-groups may take; a chunk is at least one group (0: always one)
     int xcd_swz = 1;
 };
 

@@ -88,7 +88,7 @@ int bmx_ctx_synchronize(bmx_ctx* ctx);
 /* launch-shape knobs of the counts pipeline (results never depend on them; 0 / -1 = automatic):
  * "pipe_rows" 0|8|4|2|1 (KiB of a block per work item), "pipe_unroll" 0|1|2|4|8|16, "pipe_nt" 0|1,
  * "pipe_wg" 0|64..1024 (multiples of 64; the default build carries 256, 384, 512, 640, 768), "pipe_staged" -1|0|1, "pipe_slots" 8|16,
- * "pipe_window" -1|0|N (block columns per launch), "pipe_split" -1|0|1, "direct_cols" 0..N (one-launch aggregation over small collections), "ff_window" -1|0|N (first launch window of find_first_and_sub), "pair_stream" -1|0|2|4|8 and "pair_wgs" 1..8 (shape of the streaming pairwise count kernel), "pair_loop" -1|0|1..5 and "pair_nt" 0|1 (persistent pairwise count kernel for mixed block kinds: workgroups per CU, non-temporal loads), "eq_big_shape" 0|1|2, "gap_count" -1|0|1 (counting formulation for GAP-only counts pipelines), "range_halves" 0|1 (comparison search in half-block passes), "rs_lanes" 0|2|4|8 (lanes per rank query), "rs_lines" 0|1|2 (build_rs_index also lays the vector out as rank lines: one 128-byte line per rank query), "rs_select_lines" 0|1|2 (select through the block index | the lines + octant directory | the select directory over the lines) and "rs_sdir_shift" 0|6..20 (log2 of the ones per select-directory entry; 0 = an entry per ~10 lines), "gap_pack" -1|0|1 (packed collections, see below), "eq_big" -1|0|1 (table form of bmx_slice_eq_counts), "op2_wgs" 1..8 and "op2_nt" 0..3 (streaming bit_and/or/xor/sub kernel: workgroups per CU; bit 0 / 1 = non-temporal loads / stores), "op2_loop" -1|0|1..8 (persistent bit_and/or/xor/sub kernel for mixed block kinds: workgroups per CU), "or_rows" -1|0|1 and "or_depth" 4|8 (combine_or over >= 64 sparse GAP-only operands through the vectors' tile directories: automatic | never | always; rows in flight per wave), "coll_members" -1|0|1 (lists that are SOME vectors of a prepared collection: the member directory automatic | never | whenever covered), "or_tile" 0..3, "xcd_swizzle" 0|1, "rankc_path" -1|0|1 (bmx_rank_compress / bmx_rank_decompress: automatic | ascending positions into the sorted path of bmx_vec_from_indices | whole blocks; results never depend on it).  Environment twins (BMX_PIPE_ROWS, ...) pass the same checks. */
+ * "pipe_window" -1|0|N (block columns per launch), "pipe_split" -1|0|1, "direct_cols" 0..N (one-launch aggregation over small collections), "ff_window" -1|0|N (first launch window of find_first_and_sub), "pair_stream" -1|0|2|4|8 and "pair_wgs" 1..8 (shape of the streaming pairwise count kernel), "pair_loop" -1|0|1..5 and "pair_nt" 0|1 (persistent pairwise count kernel for mixed block kinds: workgroups per CU, non-temporal loads), "eq_big_shape" 0|1|2, "gap_count" -1|0|1 (counting formulation for GAP-only counts pipelines), "range_halves" 0|1 (comparison search in half-block passes), "rs_lanes" 0|2|4|8 (lanes per rank query), "rs_lines" 0|1|2 (build_rs_index also lays the vector out as rank lines: one 128-byte line per rank query), "rs_select_lines" 0|1|2 (select through the block index | the lines + octant directory | the select directory over the lines) and "rs_sdir_shift" 0|6..20 (log2 of the ones per select-directory entry; 0 = an entry per ~10 lines), "gap_pack" -1|0|1 (packed collections, see below), "eq_big" -1|0|1 (table form of bmx_slice_eq_counts), "op2_wgs" 1..8 and "op2_nt" 0..3 (streaming bit_and/or/xor/sub kernel: workgroups per CU; bit 0 / 1 = non-temporal loads / stores), "op2_loop" -1|0|1..8 (persistent bit_and/or/xor/sub kernel for mixed block kinds: workgroups per CU), "or_rows" -1|0|1 and "or_depth" 4|8 (combine_or over >= 64 sparse GAP-only operands through the vectors' tile directories: automatic | never | always; rows in flight per wave), "coll_members" -1|0|1 (lists that are SOME vectors of a prepared collection: the member directory automatic | never | whenever covered), "or_tile" 0..3, "xcd_swizzle" 0|1, "rankc_path" -1|0|1 (bmx_rank_compress / bmx_rank_decompress: automatic | ascending positions into the sorted path of bmx_vec_from_indices | whole blocks; results never depend on it), "hits_table_kb" 0..4194304 (bmx_pipeline_run_indices: KiB of the hit table a chunk of arg-groups may take).  Environment twins (BMX_PIPE_ROWS, ...) pass the same checks. */
 int bmx_ctx_set_tuning(bmx_ctx* ctx, const char* key, int value);
 /* The context keeps freed device blocks in a size-keyed cache (results of same-shaped
  * operations re-use them instead of paying hipMalloc/hipFree, which synchronises the
@@ -402,6 +402,23 @@ int bmx_pipeline_run_results_range(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_fr
  * be NULL (counts only). */
 int bmx_pipeline_run_results_hint(bmx_ctx* ctx, bmx_pipeline* p, uint64_t from, uint64_t to, bmx_vec** results_out,
                                   uint64_t* counts_out, const bmx_vec* or_target_in, bmx_vec** or_target_out);
+/* combine_and_sub(pipe) with the hits of EVERY arg-group as ascending positions -- what combine_and_sub(BII bi, and_g, n, sub_g, m)
+ * (src/bmaggregator.h:1226-1284) feeds its iterator for group g, and find_eq(sv, value, bi) (src/bmsparsevec_algo.h:1096) for one
+ * value -- all groups concatenated in group order into one CSR: out[offsets[g] .. offsets[g + 1]) are the set bits of
+ * AND(and_g) & ~OR(sub_g) inside block columns [nb_from, nb_to) (nb_to = UINT32_MAX: all), offsets[0] = 0, offsets[ngroups] = *n.
+ * Positions are absolute (not rebased when nb_from > 0); a group with an empty AND list yields an empty segment (:1352).
+ * pipeline::set_search_count_limit is NOT applied (as in result-only runs): every group returns all its hits.
+ * Buffer rules of bmx_vec_to_indices: width = 4 (uint32_t positions; BMX_ERR_RANGE for a pipeline of more than 65,536 block
+ * columns) or 8; *n is always the total; when it exceeds cap nothing is written to out and BMX_ERR_RANGE is returned, with
+ * offsets filled, so the caller can size the buffer and call again.  offsets: HOST, ngroups + 1 entries.  One synchronise to
+ * learn the total, plus the copy-back.  The groups are processed in chunks whose (column, group) table stays within the
+ * "hits_table_kb" tuning key (12 bytes per item; default 524,288 KiB; a chunk is at least one group, 0 = always one).
+ * _dev: d_out is DEVICE memory, complete on the context's stream when the call returns; offsets (host) and d_offsets (device,
+ * ngroups + 1) may each be NULL. */
+int bmx_pipeline_run_indices(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, int width,
+                             uint64_t* offsets, void* out, uint64_t cap, uint64_t* n);
+int bmx_pipeline_run_indices_dev(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, int width,
+                                 uint64_t* offsets, uint64_t* d_offsets, void* d_out, uint64_t cap, uint64_t* n);
 /* algorithmic operand bytes one run over [nb_from, nb_to) must read
  * (8192 B per bit-block operand, 2*(len+1) B per GAP operand; NULL/FULL: 0) */
 int bmx_pipeline_operand_bytes(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to,

@@ -24,6 +24,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -737,6 +738,48 @@ public:
             if (hinted) check(bmx_pipeline_run_results_hint(ctx_->handle(), pipe.h_, range_from_, range_to_, nullptr, pipe.counts_.data(), nullptr, nullptr));
             else check(bmx_pipeline_run_counts(ctx_->handle(), pipe.h_, 0u, 0xFFFFFFFFu, pipe.counts_.data()));
         }
+    }
+    /// the hits of EVERY arg-group of the pipeline as ascending positions, all groups in one CSR: ids[offsets[g] .. offsets[g + 1])
+    /// is what combine_and_sub(bi, and_g, n, sub_g, m) (:1226-1284) feeds its iterator for group g (bmx_pipeline_run_indices: one
+    /// device run for the whole batch, only the positions cross PCIe).  Honours set_range_hint at block granularity when the
+    /// pipeline options enable search masks; a hint inside ONE block is bit-masked as well, through the vector route
+    /// (bmx_pipeline_run_results_hint).  The search count limit does not apply.
+    template <class TPipe>
+    void combine_and_sub_indices(TPipe& pipe, std::vector<size_type>& offsets, std::vector<size_type>& ids)
+    {
+        if (!pipe.is_complete()) throw error(BMX_ERR_BADARG, "pipeline is not complete()");
+        offsets.assign(pipe.size() + 1, 0); ids.clear();
+        if (!pipe.size()) return;
+        uint32_t lo = 0u, hi = 0xFFFFFFFFu;
+        if (TPipe::options_type::is_masks() && range_set_) {
+            const uint64_t nbf = range_from_ >> 16, nbt = range_to_ >> 16;
+            const bool whole = (range_from_ & 65535u) == 0 && (range_to_ & 65535u) == 65535u;
+            if (nbf == nbt && !whole) {
+                std::vector<bmx_vec*> res(pipe.size(), nullptr);
+                check(bmx_pipeline_run_results_hint(ctx_->handle(), pipe.h_, range_from_, range_to_, res.data(), nullptr, nullptr, nullptr));
+                std::vector<std::unique_ptr<BV> > owned(res.size());
+                for (size_t g = 0; g < res.size(); ++g) if (res[g]) { owned[g].reset(new BV(*ctx_)); owned[g]->adopt(res[g]); }
+                std::vector<size_type> one;
+                for (size_t g = 0; g < res.size(); ++g) {
+                    if (owned[g]) { owned[g]->to_indices(one); ids.insert(ids.end(), one.begin(), one.end()); }
+                    offsets[g + 1] = ids.size();
+                }
+                return;
+            }
+            lo = (uint32_t)(nbf < 0xFFFFFFFEull ? nbf : 0xFFFFFFFEull); hi = (uint32_t)(nbt + 1 < 0xFFFFFFFFull ? nbt + 1 : 0xFFFFFFFFull);
+        }
+        // the capacity protocol of bmx_vec_to_indices: a call into what ids can already hold; when that is too small the call has
+        // written nothing but the total and the offsets, and a second one writes into a buffer of that size
+        uint64_t n = 0;
+        ids.resize(ids.capacity());
+        const uint64_t cap = ids.size();
+        int rc = bmx_pipeline_run_indices(ctx_->handle(), pipe.h_, lo, hi, 8, offsets.data(), cap ? ids.data() : nullptr, cap, &n);
+        if (rc == BMX_ERR_RANGE && n > cap) {
+            ids.resize(n);
+            rc = bmx_pipeline_run_indices(ctx_->handle(), pipe.h_, lo, hi, 8, offsets.data(), ids.data(), n, &n);
+        }
+        if (rc != BMX_OK) { ids.clear(); check(rc); }
+        ids.resize(n);
     }
 
 private:

@@ -12,6 +12,8 @@
 //        SUB group = every other existing slice below effective_slices(); a set bit
 //        without a slice => nothing can match
 //   pipeline of many searches (batch of arg-groups, :3236,3408)   slice_scanner::find_eq_counts(values, n, counts)
+//   ... with the matching rows of every search (find_eq(sv,       slice_scanner::find_eq_indices(values, n, offsets, ids)
+//        value, bi) :1096 per value)                                  one CSR of ascending row ids for the whole batch
 //   find_gt / find_ge / find_lt / find_le / find_range             slice_scanner::find_gt(value, bv_out) ...
 //        :1135-1174 -> :2690-2880, find_gt_horizontal_u :2914         ONE pass over the planes (bmx_slice_compare,
 //   find_zero :2290, find_nonzero :4464, find_eq(sv, 0, ..) :4366     bmx_kernels4.h) instead of a chain of vector ops
@@ -129,6 +131,34 @@ public:
         pipe.complete();
         agg_.combine_and_sub(pipe);
         for (size_t q = 0; q < n; ++q) if (slot[q] != ~size_t(0)) counts[q] = pipe.get_bv_count_vector()[slot[q]];
+    }
+
+    /// a batch of find_eq(sv, value, bi) (:1096): ids[offsets[q] .. offsets[q + 1]) = the rows equal to values[q], ascending.  One
+    /// AND-SUB group per value in ONE index-list pipeline run (aggregator::combine_and_sub_indices); a value with a set bit that
+    /// has no plane gives an empty segment; value 0 goes through the comparison kernel (find_zero, :4366) and is spliced in here
+    void find_eq_indices(const uint64_t* values, size_t n, std::vector<size_type>& offsets, std::vector<size_type>& ids)
+    {
+        typedef typename aggregator<bvector>::template pipeline<agg_opt_disable_bvects_and_counts> pipe_t;
+        pipe_t pipe(*ctx_);
+        std::vector<size_t> slot(n, ~size_t(0));
+        bool any_zero = false;
+        for (size_t q = 0; q < n; ++q) {
+            if (!values[q]) { any_zero = true; continue; }
+            typename aggregator<bvector>::arg_groups g;
+            if (!add_groups(values[q], g)) continue;                     // impossible value: empty segment
+            *pipe.add() = g;
+            slot[q] = pipe.size() - 1;
+        }
+        std::vector<size_type> poff(1, 0), pids, zero;
+        if (pipe.size()) { pipe.complete(); agg_.combine_and_sub_indices(pipe, poff, pids); }
+        if (any_zero) { bvector z(*ctx_); compare(BMX_CMP_EQ, 0, 0, &z); z.to_indices(zero); }
+        offsets.assign(n + 1, 0); ids.clear();
+        if (!any_zero && pipe.size() == n) { ids.swap(pids); offsets = poff; return; }       // every value has its own group: no splice
+        for (size_t q = 0; q < n; ++q) {
+            if (!values[q]) ids.insert(ids.end(), zero.begin(), zero.end());
+            else if (slot[q] != ~size_t(0)) ids.insert(ids.end(), pids.begin() + (ptrdiff_t)poff[slot[q]], pids.begin() + (ptrdiff_t)poff[slot[q] + 1]);
+            offsets[q + 1] = ids.size();
+        }
     }
 
 private:
