@@ -20,6 +20,9 @@ argument meaning and error behaviour), layered on the C-ABI of include/bmx.h:
       combine_and_sub                               combine_and / combine_and_sub
       pipeline<agg_opt_only_counts> :222            aggregator.pipeline (add().add(bv, grp), complete())
       combine_and_sub(pipe)         :1292           aggregator.combine_and_sub(pipe)
+    bm::sparse_vector_find_mismatch        src/bmsparsevec_algo.h:656   sparse_vector_find_mismatch(a, b, null_proc)
+    bm::sparse_vector_find_first_mismatch  :478                         sparse_vector_find_first_mismatch(a, b, null_proc)
+                                                   (a, b: slice_scanner; also sparse_vector_count_mismatch)
 
 The data path is the HIP library only; there is no CPU fallback.
 """
@@ -49,7 +52,8 @@ __all__ = ["context", "bvector", "aggregator", "slice_scanner", "rs_index", "ran
            "count_xor", "count_sub", "distance_operation", "distance_matrix", "distance_matrix_dev",
            "COUNT_AND", "COUNT_XOR", "COUNT_OR", "COUNT_SUB_AB", "COUNT_SUB_BA", "COUNT_A", "COUNT_B", "BmxError", "simd_version", "device_count", "agg_run_options",
            "agg_opt_only_counts", "agg_opt_bvect_and_counts", "agg_opt_disable_bvects_and_counts",
-           "BM_UNSORTED", "BM_SORTED", "BM_SORTED_UNIFORM", "BM_UNKNOWN"]
+           "BM_UNSORTED", "BM_SORTED", "BM_SORTED_UNIFORM", "BM_UNKNOWN",
+           "sparse_vector_find_mismatch", "sparse_vector_count_mismatch", "sparse_vector_find_first_mismatch", "USE_NULL", "NO_NULL"]
 
 
 def simd_version() -> int:
@@ -1202,6 +1206,52 @@ class slice_scanner:
             for q, sl in enumerate(slot):
                 if sl >= 0: out[q] = cnt[sl]
         return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# which rows differ between two resident columns (include/bmx.h "which rows differ"; src/bmsparsevec_algo.h:478-792)
+# ---------------------------------------------------------------------------------------------------
+USE_NULL, NO_NULL = 0, 1             # bm::null_support (src/bmconst.h:231)
+
+
+def _mismatch_args(a: "slice_scanner", b: "slice_scanner"):
+    if type(a) is not slice_scanner or type(b) is not slice_scanner:
+        raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "two slice_scanner objects of one device expected")
+    if a.ctx is not b.ctx:
+        raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "the two columns live in different contexts")
+    if a.signed != b.signed:
+        raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "a signed column against an unsigned one: the planes mean different things")
+    out = []
+    for s in (a, b):
+        arr = (C.c_void_p * max(len(s.slices), 1))()
+        for i, p in enumerate(s.slices):
+            arr[i] = p._h if p is not None else None
+        out += [arr, len(s.slices), s.size(), s.not_null._h if s.not_null is not None else None]
+    return out
+
+
+def sparse_vector_find_mismatch(a: "slice_scanner", b: "slice_scanner", null_proc: int) -> bvector:
+    """bm::sparse_vector_find_mismatch(bv, sv1, sv2, null_proc), src/bmsparsevec_algo.h:656: the rows in which the two
+    columns differ, in one pass over both columns' planes.  Two signed columns compare as they are (the sign is plane 0).
+    USE_NULL without a not-NULL vector on either side is BmxError(BADARG) (include/bmx.h)."""
+    h = C.c_void_p()
+    check(lib().bmx_slice_mismatch(a.ctx._h, *_mismatch_args(a, b), int(null_proc), C.byref(h), None))
+    return bvector(a.ctx, h)
+
+
+def sparse_vector_count_mismatch(a: "slice_scanner", b: "slice_scanner", null_proc: int) -> int:
+    """the number of rows sparse_vector_find_mismatch would set; nothing is materialised"""
+    cnt = C.c_uint64()
+    check(lib().bmx_slice_mismatch(a.ctx._h, *_mismatch_args(a, b), int(null_proc), None, C.byref(cnt)))
+    return int(cnt.value)
+
+
+def sparse_vector_find_first_mismatch(a: "slice_scanner", b: "slice_scanner", null_proc: int = USE_NULL):
+    """bm::sparse_vector_find_first_mismatch(sv1, sv2, midx, null_proc), :478 -> (found, idx).  Its rule differs from the
+    vector form's (no NULL masking, no size-difference term): include/bmx.h."""
+    found, idx = C.c_int(), C.c_uint64()
+    check(lib().bmx_slice_first_mismatch(a.ctx._h, *_mismatch_args(a, b), int(null_proc), C.byref(found), C.byref(idx)))
+    return bool(found.value), int(idx.value)
 
 
 # ---------------------------------------------------------------------------------------------------

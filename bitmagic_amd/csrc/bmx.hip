@@ -19,6 +19,7 @@
 #include "bmx_kernels14.h"
 #include "bmx_kernels15.h"
 #include "bmx_kernels16.h"
+#include "bmx_kernels17.h"
 
 #include <algorithm>
 #include <atomic>
@@ -3750,6 +3751,22 @@ int bmx_pipeline_run_results_hint(bmx_ctx* ctx, bmx_pipeline* p, uint64_t from, 
     return BMX_OK;
 ABI_END }
 
+// the launch windows of a first-hit search over block columns [col_from, col_to): ascending, each four times the one before,
+// `first` columns in the first (tuning key ff_window: > 0 replaces it, < 0 = one launch); launch(c0, c1) enqueues one window
+extern "C++" { template <class Launch>
+static int ff_windows(const bmx_ctx* ctx, u32 col_from, u32 col_to, u32 first, Launch&& launch)
+{
+    if (ctx->ff_window < 0) first = col_to > col_from ? col_to - col_from : 0u;   // knob: one launch
+    else if (ctx->ff_window > 0) first = (u32)ctx->ff_window;
+    u32 c = col_from, w = std::max(first, 1u);
+    while (c < col_to) {
+        u32 e = (col_to - c <= w + w / 2u) ? col_to : c + w;                 // no tiny last window
+        int r = launch(c, e); if (r) return r;
+        c = e; w *= 4u;
+    }
+    return BMX_OK;
+} }
+
 static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and, const bmx_vec* const* src_sub, size_t n_sub,
                            bool ranged, uint64_t from, uint64_t to, int* found, uint64_t* idx)
 {
@@ -3777,17 +3794,7 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     const u32 ncv = col_to > col_from ? col_to - col_from : 0u;
     // long lists: any number of columns (windows); short lists: the size rule of use_direct
     const bool direct = use_direct(ctx, (n_and + n_sub < 24u) ? ncv : (ncv ? 1u : 0u), n_and + n_sub) != 0;
-    auto windows = [&](u32 first, auto&& launch) -> int {
-        if (ctx->ff_window < 0) first = ncv;                                 // knob: one launch
-        else if (ctx->ff_window > 0) first = (u32)ctx->ff_window;
-        u32 c = col_from, w = std::max(first, 1u);
-        while (c < col_to) {
-            u32 e = (col_to - c <= w + w / 2u) ? col_to : c + w;             // no tiny last window
-            int r = launch(c, e); if (r) return r;
-            c = e; w *= 4u;
-        }
-        return BMX_OK;
-    };
+    auto windows = [&](u32 first, auto&& launch) -> int { return ff_windows(ctx, col_from, col_to, first, launch); };
     if (direct) {
         // many operands: a workgroup of 8 waves per column straight from the descriptor tables (k_direct); 64 columns first
         // (a hit in the first blocks is answered after ~1/8 of what two workgroups per CU would read)
@@ -4042,6 +4049,103 @@ int bmx_slice_compare_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t 
     default: kp = CMP_NONZERO; mode = SIGN_NEG_ALL; break;                                          // any magnitude bit, or negative (-1 = sign only)
     }
     return slice_compare_impl(ctx, mag, nmag, kp, b0, b1, size, not_null, admits0 ? 1 : 0, sign, mode, result, count, nullptr);
+ABI_END }
+
+// sparse_vector_find_mismatch / sparse_vector_find_first_mismatch over two resident columns (bmx_kernels17.h): shared body of
+// bmx_slice_mismatch (result and / or count) and bmx_slice_first_mismatch (found, idx).  One operand table holds both plane
+// lists, padded to P = max(na, nb) rows each, and the two not-NULL vectors.
+static int slice_mismatch_impl(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, uint64_t size_a, const bmx_vec* nn_a,
+                               const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* nn_b, int null_proc,
+                               bool first, bmx_vec** result, uint64_t* count, int* found, uint64_t* idx)
+{
+    ARGCHK(ctx && (na == 0 || a) && (nb == 0 || b) && na <= 65 && nb <= 65);
+    ARGCHK(first ? (found && idx) : (result || count));
+    if (result) *result = nullptr;
+    if (count) *count = 0;
+    if (first) { *found = 0; *idx = 0; }
+    if (null_proc != BMX_USE_NULL && null_proc != BMX_NO_NULL) { g_last_error = "null_proc is neither BMX_USE_NULL nor BMX_NO_NULL"; return BMX_ERR_BADARG; }
+    if (!first && null_proc == BMX_USE_NULL && !nn_a && !nn_b) {
+        // (:760-788: the reference inverts an empty vector of the whole address range there -- every position up to id_max)
+        g_last_error = "BMX_USE_NULL without a not-NULL vector on either side: the reference sets every position up to id_max, which no device vector holds";
+        return BMX_ERR_BADARG;
+    }
+    int rc = set_dev(ctx); if (rc) return rc;
+    const size_t P = std::max(na, nb);
+    std::vector<const bmx_vec*> list(2 * P + 2, nullptr);
+    for (size_t i = 0; i < na; ++i) list[i] = a[i];
+    for (size_t i = 0; i < nb; ++i) list[P + i] = b[i];
+    list[2 * P] = nn_a; list[2 * P + 1] = nn_b;
+    OperandTable ops;
+    if ((rc = operand_list(ctx, list.data(), list.size(), nullptr, 0, true, &ops))) return rc;
+    const uint64_t size_hi = std::max(size_a, size_b), size_lo = first ? size_hi : std::min(size_a, size_b);
+    uint64_t nblocks64 = (size_hi + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    const uint32_t ncols = (uint32_t)nblocks64;
+    if (!P || !ncols) return result ? vec_all_null(ctx, size_hi, ncols, result) : BMX_OK;   // no planes at all / no rows: empty result, count 0, not found
+    // the NULL term (bmx_kernels17.h); an absent side of the XOR is ones[0, fill)
+    int null_mode = MM_NULL_NONE; uint64_t fill = 0;
+    if (nn_a || nn_b) {
+        if (null_proc == BMX_NO_NULL) null_mode = first ? MM_NULL_NONE : MM_NULL_AND_OR;
+        else {
+            null_mode = MM_NULL_OR_XOR;
+            // vector form: the column's own size (:770-787); first mismatch: the OTHER column's size (:515-526)
+            if (!nn_b) fill = first ? size_b : size_a;
+            else if (!nn_a) fill = first ? size_a : size_b;
+        }
+    }
+    Owned<bmx_vec> v; BlockStat* st = nullptr; u32* offs = nullptr;
+    if (result && (rc = result_begin(ctx, size_hi, ncols, &v, &st, &offs))) return rc;
+    DevBuf d_tab(ctx);
+    if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
+#define MM_LAUNCH(c0, c1, ending) \
+    hipLaunchKernelGGL(k_slice_mismatch, dim3(((c1) - (c0) + 3) / 4), dim3(256), 0, ctx->stream, \
+                       ops.d_descs, ops.d_nblk, (u32)P, (u32)(c0), (u32)(c1), size_lo, size_hi, null_mode, fill, ending, ctx->xcd_swz, \
+                       v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots, ctx->d_small)
+    if (first) {
+        // the windows of find_first_impl, all enqueued at once: a wave per column, first window = 2 waves per CU
+        hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
+        if (e == hipSuccess)
+            rc = ff_windows(ctx, 0u, ncols, 512u, [&](u32 c0, u32 c1) {
+                MM_LAUNCH(c0, c1, MM_FIRST);
+                hipError_t le = hipGetLastError();
+                return le == hipSuccess ? BMX_OK : fail_hip(le, "k_slice_mismatch", __LINE__);
+            });
+        if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
+        hipError_t e2 = hipStreamSynchronize(ctx->stream);
+        if (rc) return rc;
+        if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, "bmx_slice_first_mismatch", __LINE__);
+        if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
+        return BMX_OK;
+    }
+    MM_LAUNCH(0u, ncols, result ? MM_STORE : MM_COUNT);
+#undef MM_LAUNCH
+    KCHK();
+    if (!result) {
+        hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    d_tab.reset();                                          // (before the count pass below allocates)
+    if (result) {
+        *result = v.release();
+        if (count) { rc = bmx_count(ctx, *result, count); if (rc) return rc; }
+    } else *count = ctx->h_small[0];
+    return BMX_OK;
+}
+
+int bmx_slice_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, uint64_t size_a, const bmx_vec* not_null_a,
+                       const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* not_null_b, int null_proc,
+                       bmx_vec** result, uint64_t* count)
+{ ABI_TRY
+    return slice_mismatch_impl(ctx, a, na, size_a, not_null_a, b, nb, size_b, not_null_b, null_proc, false, result, count, nullptr, nullptr);
+ABI_END }
+
+int bmx_slice_first_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, uint64_t size_a, const bmx_vec* not_null_a,
+                             const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* not_null_b, int null_proc,
+                             int* found, uint64_t* idx)
+{ ABI_TRY
+    return slice_mismatch_impl(ctx, a, na, size_a, not_null_a, b, nb, size_b, not_null_b, null_proc, true, nullptr, nullptr, found, idx);
 ABI_END }
 
 // counts[q] = rows equal to values[q]: one pass over the planes whatever the number of queries (k_slice_eq_counts:

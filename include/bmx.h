@@ -316,6 +316,43 @@ int bmx_slice_compare_stat(bmx_ctx* ctx, const bmx_vec* const* slices, size_t ns
 int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* values, size_t n,
                         uint64_t size, const bmx_vec* not_null, uint64_t* counts);
 
+/* ---- which rows differ between two resident columns (bmx_kernels17.h) ----
+ * A column is what bmx_slice_compare takes: a[i] = device vector of bit-plane i or NULL, na planes, size_a rows, not_null_a or
+ * NULL.  P = max(na, nb); an absent plane counts as all zeros; D = OR over i < P of (A_i ^ B_i).  Two signed columns compare as
+ * they are (the sign is plane 0).  One pass over both columns' planes: every plane block is read once, nothing intermediate is
+ * written (the reference runs a whole-vector XOR and OR per plane, then up to three more passes for the NULL rule).
+ *
+ * bmx_slice_mismatch = bm::sparse_vector_find_mismatch(bv, sv1, sv2, null_proc), src/bmsparsevec_algo.h:656-792:
+ *   M = D | ones[min(size_a, size_b), max(size_a, size_b))                                   :716-731, before the NULL rule
+ *   BMX_NO_NULL  (:740-759)  both not-NULL vectors: M &= (N_a | N_b); one: M &= N; none: unchanged
+ *   BMX_USE_NULL (:760-788)  both: M |= N_a ^ N_b; only N_a: M |= ones[0, size_a) & ~N_a; only N_b: the same with b
+ *   The result has max(size_a, size_b) bits; operand bits at or beyond that are ignored (a sparse_vector has none).
+ *   result may be NULL (count only: nothing is materialised); count may be NULL; not both.
+ *   Two differences from the reference:
+ *     - BMX_USE_NULL with NO not-NULL vector on either side: the reference inverts an empty vector of the whole address range
+ *       and ORs it in, so every position up to bm::id_max is set (:781-787).  No device vector holds that: BMX_ERR_BADARG.
+ *     - blocks are stored by the rule of bmx_slice_compare's results (NULL / FULL / GAP / bit by content); the reference leaves
+ *       bit-blocks.  Representation only: the set of positions is the same.
+ *
+ * bmx_slice_first_mismatch = bm::sparse_vector_find_first_mismatch(sv1, sv2, midx, null_proc), :478-636 -- a DIFFERENT rule,
+ * kept as the reference has it: *idx = lowest set bit of F = D | T, *found = whether there is one.
+ *   BMX_USE_NULL  both: T = N_a ^ N_b; only N_a: T = N_a ^ ones[0, size_b) -- the OTHER column's size (:515-526);
+ *                 only N_b: T = N_b ^ ones[0, size_a); none: T = 0.          BMX_NO_NULL: T = 0.
+ *   No NULL masking and no size-difference term: two columns of different length with equal planes and no not-NULL vectors
+ *   have no first mismatch.  (The reference loops over sv1's planes only -- for two containers of one type that is P.)
+ *   Block columns are visited in ascending windows enqueued at once, as bmx_find_first_and_sub does (tuning key ff_window).
+ *
+ * BMX_ERR_BADARG: null context, a vector of another context, na or nb > 65, an unknown null_proc, neither result nor count,
+ * and the BMX_USE_NULL case above.  na == nb == 0, or both sizes 0: all-clear result, count 0, not found. */
+#define BMX_USE_NULL 0   /* bm::use_null, src/bmconst.h:231 */
+#define BMX_NO_NULL  1   /* bm::no_null */
+int bmx_slice_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, uint64_t size_a, const bmx_vec* not_null_a,
+                       const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* not_null_b, int null_proc,
+                       bmx_vec** result /* or NULL */, uint64_t* count /* or NULL */);
+int bmx_slice_first_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, uint64_t size_a, const bmx_vec* not_null_a,
+                             const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* not_null_b, int null_proc,
+                             int* found, uint64_t* idx);
+
 /* ---- packed collections: a column-major copy of the GAP run lists of a SET of vectors (bmx_kernels6.h, bmx_kernels8.h) ----
  * Vectors are immutable and device-resident, so the library owns their layout.  combine_or / combine_and / combine_and_sub
  * and pipelines over many operands made of GAP (+ NULL / FULL) blocks read thousands of separate slabs in small pieces

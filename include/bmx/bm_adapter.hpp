@@ -17,6 +17,7 @@
 
 #include "bvector.hpp"
 #include "group.hpp"
+#include "sv_algo.hpp"
 
 namespace bmx {
 
@@ -529,5 +530,38 @@ private:
     uint64_t epoch_ = 1;                 // one per public operation
     struct op_scope { device_aggregator* a; explicit op_scope(device_aggregator* x) : a(x) { ++a->epoch_; } };
 };
+
+/// bm::sparse_vector_find_mismatch(bv, sv1, sv2, null_proc) (src/bmsparsevec_algo.h:656) over two HOST containers, the
+/// reference's argument order behind the context: both columns' planes are uploaded (upload_slices), compared in one pass on
+/// the device (bmx/sv_algo.hpp) and the result is installed into the host vector.  The two differences from the reference are
+/// those of bmx_slice_mismatch (include/bmx.h).
+template <class SV1, class SV2>
+void sparse_vector_find_mismatch(context& ctx, typename SV1::bvector_type& bv, const SV1& sv1, const SV2& sv2, bm::null_support null_proc)
+{
+    std::vector<bvector> st1, st2; std::vector<const bvector*> sl1, sl2; const bvector* n1 = nullptr; const bvector* n2 = nullptr;
+    upload_slices(sv1, ctx, st1, sl1, &n1);
+    upload_slices(sv2, ctx, st2, sl2, &n2);
+    slice_scanner a(ctx), b(ctx);
+    a.bind(sl1, sv1.size(), n1); b.bind(sl2, sv2.size(), n2);
+    bvector r(ctx);
+    sparse_vector_find_mismatch(r, a, b, null_proc == bm::use_null ? use_null : no_null);
+    download(r, bv);
+}
+
+/// bm::sparse_vector_find_first_mismatch(sv1, sv2, midx, null_proc) (:478) over two host containers
+template <class SV>
+bool sparse_vector_find_first_mismatch(context& ctx, const SV& sv1, const SV& sv2, typename SV::size_type& midx,
+                                       bm::null_support null_proc = bm::use_null)
+{
+    std::vector<bvector> st1, st2; std::vector<const bvector*> sl1, sl2; const bvector* n1 = nullptr; const bvector* n2 = nullptr;
+    upload_slices(sv1, ctx, st1, sl1, &n1);
+    upload_slices(sv2, ctx, st2, sl2, &n2);
+    slice_scanner a(ctx), b(ctx);
+    a.bind(sl1, sv1.size(), n1); b.bind(sl2, sv2.size(), n2);
+    size_type idx = 0;
+    if (!sparse_vector_find_first_mismatch(a, b, idx, null_proc == bm::use_null ? use_null : no_null)) return false;
+    midx = (typename SV::size_type)idx;
+    return true;
+}
 
 } // namespace bmx

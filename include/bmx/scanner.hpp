@@ -62,6 +62,10 @@ public:
     }
     size_t effective_slices() const noexcept { return slices_.size(); }
     size_type size() const noexcept { return size_; }
+    /// what bind() was given (read-only): the planes, the not-NULL vector (nullptr: none) and the context
+    const std::vector<const bvector*>& slices() const noexcept { return slices_; }
+    const bvector* not_null() const noexcept { return (not_null_ && !not_null_->empty_handle()) ? not_null_ : nullptr; }
+    ctx_type& ctx() const noexcept { return *ctx_; }
 
     // ---- comparison searches (unsigned values): one pass over the planes ----
     void find_gt(uint64_t value, bvector& bv_out) { compare(BMX_CMP_GT, value, 0, &bv_out); }            // :2690
