@@ -1008,11 +1008,15 @@ class slice_scanner:
     effective_slices(); size = sv.size() (rows; default: the longest slice); not_null = sv.get_null_bvector().
     A batch of equality searches is one counts-only pipeline launch; a comparison search is one pass over the planes."""
 
+    signed = False                   # (the group scanner has no signed form)
+
     def __init__(self, ctx: context, slices: Sequence[bvector | None], size: int | None = None, not_null: bvector | None = None,
                  signed: bool = False):
         """signed: the planes of a bm::sparse_vector<int, ..> -- slices[0] is the sign, slices[1..] the magnitude
-        (base_sparse_vector::s2u, src/bmbmatrix.h:2536): the comparison searches then take signed bounds
-        (find_gt_horizontal_s, src/bmsparsevec_algo.h:1484,3033)"""
+        (base_sparse_vector::s2u, src/bmbmatrix.h:2536).  EVERY search then takes signed values: the comparison searches take
+        signed bounds (find_gt_horizontal_s, src/bmsparsevec_algo.h:1484,3033), and the equality family (find_eq, find_first_eq,
+        find_eq_in, find_eq_indices, find_eq_counts) maps the value through s2u before it picks the planes, as the reference
+        does (prepare_and_sub_aggregator, src/bmsparsevec_algo.h:2603,2654): find_eq(-3) looks for -3, not for a bit pattern"""
         self.ctx, self.slices = ctx, list(slices)
         self.agg = aggregator(ctx)
         self.not_null = not_null
@@ -1034,7 +1038,16 @@ class slice_scanner:
         check(lib().bmx_slice_eq_counts(self.ctx._h, arr, len(self.slices), _ptr(vals), vals.size, self.size(),
                                         self.not_null._h if self.not_null is not None else None, _ptr(out)))
 
+    def _pattern(self, value: int) -> int:
+        """the bits the planes hold for `value`: the value itself, or s2u(value) for a signed container (sign in bit 0)"""
+        if not self.signed:
+            return value
+        if not -(1 << 63) <= value < (1 << 63):
+            raise BmxError(_ffi.ERR_RANGE, "Incorrect range or index", "signed 64-bit values only")
+        return value << 1 if value >= 0 else ((-(value + 1)) << 1) | 1
+
     def _groups(self, value: int):
+        value = self._pattern(value)
         if value <= 0:
             raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "value 0 has no AND group: find_eq(0) goes through the comparison kernel")
         a = []
@@ -1097,7 +1110,7 @@ class slice_scanner:
             pipe.complete()
             self.agg.combine_and_sub(pipe)
             return pipe.get_or_target()
-        return acc if acc is not None else self._compare(CMP_GT, (1 << 64) - 1)       # nothing to look for: empty result
+        return acc if acc is not None else self._compare(CMP_GT, (1 << (63 if self.signed else 64)) - 1)   # nothing to look for: empty result
 
     def decompress(self, bv: "bvector", rs_idx: "rs_index | None" = None) -> "bvector":
         """scanner.decompress(sv, bv)  src/bmsparsevec_algo.h:4525: a result in the rank space of a compressed container back to its
@@ -1181,7 +1194,7 @@ class slice_scanner:
         if method == "auto":
             method = "transpose" if self._can_transpose() else "pipeline"
         if method == "transpose":
-            vals = np.ascontiguousarray([int(v) for v in values], np.uint64)
+            vals = np.ascontiguousarray([self._pattern(int(v)) for v in values], np.uint64)
             arr = (C.c_void_p * max(len(self.slices), 1))()
             for i, p in enumerate(self.slices):
                 arr[i] = p._h if p is not None else None

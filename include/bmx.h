@@ -302,7 +302,8 @@ int bmx_slice_compare(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices
  * of the reference's encoding (v >= 0 -> v << 1, v < 0 -> ((-(v + 1)) << 1) | 1: base_sparse_vector::s2u, src/bmbmatrix.h:2536);
  * bounds are signed.  What the reference builds from whole-vector passes (find_gt_horizontal_s, src/bmsparsevec_algo.h:1484,
  * 3033-3160, and find_ge / lt / le / range on top of it) is the same one pass over the magnitude planes combined with the sign
- * block in the kernel.  NULL rows (stored as +0) drop out wherever the predicate admits 0. */
+ * block in the kernel.  NULL rows (stored as +0) drop out wherever the predicate admits 0.  At 64-bit width (sign + 63 or 64
+ * magnitude planes, bounds down to INT64_MIN) the library follows plain integer comparison of the rows' values. */
 int bmx_slice_compare_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int pred, int64_t v0, int64_t v1,
                              uint64_t size, const bmx_vec* not_null, bmx_vec** result, uint64_t* count);
 /* bmx_slice_compare (count only) that also reports the plane bytes the walk actually had to read -- it stops in a block column

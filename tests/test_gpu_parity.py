@@ -2258,6 +2258,10 @@ def test_signed_scanner_inlist_invert_vs_reference_golden(ctx, golden, with_null
         for e in g["cmp"]["eq"]:
             assert sc.count(bm.CMP_EQ, e["v"]) == e["count"]
             chk(sc._compare(bm.CMP_EQ, e["v"]), e)
+            t, found = sc.find_eq(e["v"])                       # the public call takes the signed value as well
+            assert found == (e["count"] > 0), e
+            if t is not None: chk(t, e)
+            else: assert e["count"] == 0, e
         for e in g["range"]:
             chk(sc.find_range(e["from"], e["to"]), e)
             assert sc.count(bm.CMP_RANGE, e["from"], e["to"]) == e["count"]
