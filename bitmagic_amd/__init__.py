@@ -1220,6 +1220,59 @@ class slice_scanner:
                 if sl >= 0: out[q] = cnt[sl]
         return out
 
+    def _range_counts_call(self, arr, lo, hi, out):
+        fn = lib().bmx_slice_range_counts_signed if self.signed else lib().bmx_slice_range_counts
+        check(fn(self.ctx._h, arr, len(self.slices), _ptr(lo), _ptr(hi), lo.size, self.size(),
+                 self.not_null._h if self.not_null is not None else None, _ptr(out)))
+
+    def find_range_counts(self, lo, hi) -> np.ndarray:
+        """counts[q] = not-NULL rows with lo[q] <= value <= hi[q] (closed; a reversed pair is swapped, as find_range does,
+        src/bmsparsevec_algo.h:2862): what a loop of find_range + count() computes, in one pass over the planes per 8 distinct
+        thresholds instead of one per range (bmx_slice_range_counts).  Signed bounds for a signed container."""
+        tmin, tmax = (-(1 << 63), (1 << 63) - 1) if self.signed else (0, (1 << 64) - 1)
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if len(lo) != len(hi):
+            raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "lo and hi differ in length")
+        if any(not tmin <= v <= tmax for v in lo + hi):
+            raise BmxError(_ffi.ERR_RANGE, "Incorrect range or index", ("signed" if self.signed else "unsigned") + " 64-bit values only")
+        dt = np.int64 if self.signed else np.uint64
+        lo, hi = np.array(lo, dt), np.array(hi, dt)
+        out = np.zeros(lo.size, np.uint64)
+        arr = (C.c_void_p * max(len(self.slices), 1))()
+        for i, p in enumerate(self.slices):
+            arr[i] = p._h if p is not None else None
+        if lo.size:
+            self._range_counts_call(arr, lo, hi, out)
+        return out
+
+    def range_counts_stat(self, lo, hi):
+        """-> (counts, plane_bytes, launches): find_range_counts of an unsigned container through the batch kernel, with the
+        launches it enqueued over the planes and the plane bytes they loaded (bmx_slice_range_counts_stat)"""
+        lo, hi = np.array([int(v) for v in lo], np.uint64), np.array([int(v) for v in hi], np.uint64)
+        out = np.zeros(lo.size, np.uint64)
+        arr = (C.c_void_p * max(len(self.slices), 1))()
+        for i, p in enumerate(self.slices):
+            arr[i] = p._h if p is not None else None
+        pb, nl = C.c_uint64(), C.c_uint32()
+        check(lib().bmx_slice_range_counts_stat(self.ctx._h, arr, len(self.slices), _ptr(lo), _ptr(hi), lo.size, self.size(),
+                                                self.not_null._h if self.not_null is not None else None, _ptr(out), C.byref(pb), C.byref(nl)))
+        return out, pb.value, nl.value
+
+    def histogram(self, edges) -> np.ndarray:
+        """len(edges) - 1 bins [edges[k], edges[k + 1]) over ascending edges: counts[k] = not-NULL rows in bin k; a bin whose
+        edges are equal is empty.  One find_range_counts call over the closed ranges [edges[k], edges[k + 1] - 1]."""
+        e = [int(v) for v in edges]
+        tmin, tmax = (-(1 << 63), (1 << 63) - 1) if self.signed else (0, (1 << 64) - 1)
+        if any(not tmin <= v <= tmax for v in e):
+            raise BmxError(_ffi.ERR_RANGE, "Incorrect range or index", ("signed" if self.signed else "unsigned") + " 64-bit values only")
+        if any(b < a for a, b in zip(e, e[1:])):
+            raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "histogram edges must ascend")
+        out = np.zeros(max(len(e) - 1, 0), np.uint64)
+        bins = [k for k in range(len(e) - 1) if e[k] < e[k + 1]]
+        if bins:
+            out[bins] = self.find_range_counts([e[k] for k in bins], [e[k + 1] - 1 for k in bins])
+        return out
+
 
 # ---------------------------------------------------------------------------------------------------
 # which rows differ between two resident columns (include/bmx.h "which rows differ"; src/bmsparsevec_algo.h:478-792)
@@ -1669,6 +1722,10 @@ class gslice_scanner(slice_scanner):
     def _eq_counts_call(self, arr, vals, out):
         check(lib().bmx_gslice_eq_counts(self.grp._h, arr, len(self.slices), _ptr(vals), vals.size, self.size(),
                                          self.not_null._h if self.not_null is not None else None, _ptr(out)))
+
+    def _range_counts_call(self, arr, lo, hi, out):
+        check(lib().bmx_gslice_range_counts(self.grp._h, arr, len(self.slices), _ptr(lo), _ptr(hi), lo.size, self.size(),
+                                            self.not_null._h if self.not_null is not None else None, _ptr(out)))
 
     def _compare(self, pred: int, v0: int = 0, v1: int = 0, count_only: bool = False):
         if v0 < 0 or v1 < 0 or v0 >= 1 << 64 or v1 >= 1 << 64:

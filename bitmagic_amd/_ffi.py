@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BMX_LIB") or os.path.join(_HERE, "lib", "libbmx.so")
 
 OK, ERR_BADALLOC, ERR_BADARG, ERR_RANGE, ERR_DEVICE = 0, 1, 2, 3, 4
+RC_BATCH_MAX = 8            # BMX_RC_BATCH_MAX of include/bmx.h: thresholds per launch of bmx_slice_range_counts
 
 
 class BmxError(RuntimeError):
@@ -95,6 +96,9 @@ def lib() -> C.CDLL:
         "bmx_slice_compare_signed": (i32, [vp, P(vp), C.c_size_t, i32, C.c_int64, C.c_int64, u64, vp, P(vp), P(u64)]),
         "bmx_slice_compare_stat": (i32, [vp, P(vp), C.c_size_t, i32, u64, u64, u64, vp, P(u64), P(u64)]),
         "bmx_slice_eq_counts": (i32, [vp, P(vp), C.c_size_t, vp, C.c_size_t, u64, vp, vp]),
+        "bmx_slice_range_counts": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp]),
+        "bmx_slice_range_counts_stat": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp, P(u64), P(u32)]),
+        "bmx_slice_range_counts_signed": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp]),
         "bmx_slice_mismatch": (i32, [vp, P(vp), C.c_size_t, u64, vp, P(vp), C.c_size_t, u64, vp, i32, P(vp), P(u64)]),
         "bmx_slice_first_mismatch": (i32, [vp, P(vp), C.c_size_t, u64, vp, P(vp), C.c_size_t, u64, vp, i32, P(i32), P(u64)]),
         "bmx_collection_prepare": (i32, [vp, P(vp), C.c_size_t, i32]),
@@ -159,6 +163,7 @@ def lib() -> C.CDLL:
         "bmx_gfind_first_and_sub": (i32, [vp, P(vp), C.c_size_t, P(vp), C.c_size_t, P(i32), P(u64)]),
         "bmx_gslice_compare": (i32, [vp, P(vp), C.c_size_t, i32, u64, u64, u64, vp, P(vp), P(u64)]),
         "bmx_gslice_eq_counts": (i32, [vp, P(vp), C.c_size_t, vp, C.c_size_t, u64, vp, vp]),
+        "bmx_gslice_range_counts": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp]),
         "bmx_gpipeline_create": (i32, [vp, P(vp), P(u32), P(vp), P(u32), C.c_size_t, P(vp)]),
         "bmx_gpipeline_destroy": (i32, [vp, vp]),
         "bmx_gpipeline_run_counts": (i32, [vp, vp, P(u64)]),

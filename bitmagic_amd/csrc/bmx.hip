@@ -20,6 +20,7 @@
 #include "bmx_kernels15.h"
 #include "bmx_kernels16.h"
 #include "bmx_kernels17.h"
+#include "bmx_kernels18.h"
 
 #include <algorithm>
 #include <atomic>
@@ -890,6 +891,7 @@ static int ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
     else if (k == "and_rows_nt") ctx->and_rows_nt = value != 0;
     else if (k == "and_rows_ipw") { ARGCHK(value >= 0 && value <= 64); ctx->and_rows_ipw = value; }
     else if (k == "ff_window") { ARGCHK(value >= -1); ctx->ff_window = value; }
+    else if (k == "rc_batch") { ARGCHK(value >= -1 && value <= BMX_RC_BATCH_MAX); ctx->rc_batch = value; }
     else if (k == "or_window") { ARGCHK(value >= -9); ctx->or_window = value; }
     else if (k == "gap_pack") { ARGCHK(value >= -1 && value <= 1); ctx->gap_pack = value; }
     else if (k == "coll_members") { ARGCHK(value >= -1 && value <= 1); ctx->coll_members = value; ++ctx->coll_gen; }
@@ -1059,7 +1061,7 @@ int bmx_ctx_create(int device, void* stream, bmx_ctx** out)
     // an invalid value is ignored (the default stays)
     static const char* const env_keys[][2] = {
         {"BMX_PIPE_UNROLL", "pipe_unroll"}, {"BMX_PIPE_ROWS", "pipe_rows"}, {"BMX_PIPE_NT", "pipe_nt"},
-        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}, {"BMX_HITS_TABLE_KB", "hits_table_kb"}};
+        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_RC_BATCH", "rc_batch"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}, {"BMX_HITS_TABLE_KB", "hits_table_kb"}};
     for (auto& kv : env_keys)
         if (const char* e = getenv(kv[0])) (void)ctx_set_tuning(ctx.get(), kv[1], atoi(e));
     g_last_error.clear();
@@ -4287,6 +4289,192 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q) if (slot[q] >= 0) counts[q] = ucount[(size_t)slot[q]];
     return BMX_OK;
+ABI_END }
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------
+// bmx_slice_range_counts / bmx_slice_range_counts_signed: n range counts in ceil(thresholds / T) passes over the planes
+// (k_slice_le_counts, bmx_kernels18.h) where a loop of find_range + count() (src/bmsparsevec_algo.h:2862) reads them n times
+// ---------------------------------------------------------------------------
+// The plan (plain C++, no HIP call).  LE_c(t) = valid rows of sign class c (0: sign clear -- all rows of an unsigned column --,
+// 1: sign set) whose magnitude is <= t.  Every range is one or two terms  LE_c(hi) - LE_c(lo):
+//   unsigned [a, b]        class 0, magnitudes [a, b]
+//   signed   [a, b]        b >= 0: class 0, magnitudes [max(a, 0), b];   a < 0: class 1, magnitudes [-(min(b, -1) + 1), -(a + 1)]
+//                          (a negative v has magnitude -(v + 1) = ~v in uint64_t: INT64_MIN needs no negation of itself)
+// and a magnitude interval [m_lo, m_hi] is LE(m_hi) - (m_lo > 0 ? LE(m_lo - 1) : 0).  thr = the sorted distinct thresholds the
+// kernel has to count; a threshold at or above the largest magnitude the planes can hold counts every valid row of its class
+// (LE_ALL: the kernel's totals) and takes no accumulator.
+enum : int64_t { LE_ALL = -1, LE_NONE = -2 };
+struct RangeTerm { size_t q; int cls; int64_t hi, lo; };               // counts[q] += LE_cls(hi) - LE_cls(lo); hi, lo: index into thr, LE_ALL or LE_NONE
+struct RangePlan { std::vector<uint64_t> thr; std::vector<RangeTerm> terms; };
+// default policy (rc_batch = 0): fewer ranges than this go through bmx_slice_compare, one call each (TUNING.md, rc_batch)
+static const size_t RC_LOOP_BELOW = 2;
+
+// lo / hi: the bounds as the caller passed them (signed: the int64_t bit patterns); nmag: magnitude planes
+static RangePlan range_plan(const uint64_t* lo, const uint64_t* hi, size_t n, bool sgn, size_t nmag)
+{
+    const uint64_t mag_max = nmag >= 64 ? ~0ull : (1ull << nmag) - 1ull;
+    struct Interval { size_t q; int cls; uint64_t m_lo, m_hi; };
+    std::vector<Interval> iv;
+    iv.reserve(sgn ? 2 * n : n);
+    for (size_t q = 0; q < n; ++q) {
+        if (!sgn) {
+            uint64_t a = lo[q], b = hi[q];
+            if (b < a) std::swap(a, b);                                 // bm::xor_swap(from, to), :2872
+            iv.push_back({q, 0, a, b});
+        } else {
+            int64_t a = (int64_t)lo[q], b = (int64_t)hi[q];
+            if (b < a) std::swap(a, b);
+            if (b >= 0) iv.push_back({q, 0, (uint64_t)std::max<int64_t>(a, 0), (uint64_t)b});
+            if (a < 0) iv.push_back({q, 1, ~(uint64_t)std::min<int64_t>(b, -1), ~(uint64_t)a});
+        }
+    }
+    RangePlan p;
+    for (const Interval& i : iv) {
+        if (i.m_hi < mag_max) p.thr.push_back(i.m_hi);
+        if (i.m_lo > 0 && i.m_lo - 1 < mag_max) p.thr.push_back(i.m_lo - 1);
+    }
+    std::sort(p.thr.begin(), p.thr.end());
+    p.thr.erase(std::unique(p.thr.begin(), p.thr.end()), p.thr.end());
+    auto ref = [&](uint64_t t) -> int64_t {
+        return t >= mag_max ? (int64_t)LE_ALL : (int64_t)(std::lower_bound(p.thr.begin(), p.thr.end(), t) - p.thr.begin());
+    };
+    p.terms.reserve(iv.size());
+    for (const Interval& i : iv) p.terms.push_back({i.q, i.cls, ref(i.m_hi), i.m_lo > 0 ? ref(i.m_lo - 1) : (int64_t)LE_NONE});
+    return p;
+}
+
+// one launch: LE of nthr <= BMX_RC_BATCH_MAX thresholds into d_counts (and the valid rows into d_totals, where not null); the
+// smallest instantiation that holds them (short batches pay for no idle accumulators)
+static int le_counts_launch(bmx_ctx* ctx, const LeOperand* d_ops, u32 nmag, u32 ncols, bool sgn, const uint64_t* thr, u32 nthr,
+                            uint64_t size, int has_nn, u64* d_counts, u64* d_totals, u64* d_stat)
+{
+    const u32 nitems = ncols * 8u, grid = std::min<u32>((nitems + 3u) / 4u, 2048u);
+#define LE_GO(TT) do { \
+        LeThresholds<TT> t; \
+        for (u32 j = 0; j < (u32)TT; ++j) t.t[j] = j < nthr ? thr[j] : 0ull; \
+        if (sgn) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_le_counts<TT, 1, true>), dim3(grid), dim3(256), 0, ctx->stream, d_ops, nmag, ncols, t, nthr, size, has_nn, d_counts, d_totals, d_stat); \
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_le_counts<TT, 1, false>), dim3(grid), dim3(256), 0, ctx->stream, d_ops, nmag, ncols, t, nthr, size, has_nn, d_counts, d_totals, d_stat); \
+    } while (0)
+    if (nthr <= 4u) LE_GO(4); else LE_GO(BMX_RC_BATCH_MAX);
+#undef LE_GO
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? BMX_OK : fail_hip(e, "k_slice_le_counts", __LINE__);
+}
+
+// shared body: mag = the magnitude planes, sign = the sign plane of a signed container (or null)
+static int range_counts_impl(bmx_ctx* ctx, const bmx_vec* const* mag, size_t nmag, const bmx_vec* sign, bool sgn,
+                             const uint64_t* lo, const uint64_t* hi, size_t n, uint64_t size, const bmx_vec* not_null, uint64_t* counts,
+                             uint64_t* plane_bytes = nullptr, uint32_t* launches = nullptr)
+{
+    if (plane_bytes) *plane_bytes = 0;
+    if (launches) *launches = 0;
+    int rc = set_dev(ctx); if (rc) return rc;
+    const uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    const uint32_t ncols = (uint32_t)nblocks64;
+    const RangePlan plan = range_plan(lo, hi, n, sgn, nmag);
+    const size_t NC = sgn ? 2 : 1, K = plan.thr.size();
+    std::vector<uint64_t> res(3 + NC * K, 0);                            // [0], [1]: valid rows per sign class; [2]: bytes loaded; then LE per threshold (x NC)
+    if (ncols) {
+        std::vector<LeOperand> ops(nmag + 2);
+        memset(ops.data(), 0, ops.size() * sizeof(LeOperand));
+        std::vector<DevBuf> bufs;
+        bufs.reserve(nmag + 2);
+        DevBuf d_ops(ctx), d_cnt(ctx);
+        auto enqueue = [&]() -> int {
+            int r;
+            // operands holding GAP blocks are expanded to raw words once (bmx_kernels18.h); the others are read through their tables
+            for (size_t i = 0; i < nmag + 2; ++i) {
+                const bmx_vec* v = i < nmag ? mag[i] : (i == nmag ? sign : not_null);
+                if (!v) continue;
+                ops[i].nblk = v->nblocks;
+                if (!v->counts[BMX_GAP]) { ops[i].desc = v->d_desc; continue; }
+                bufs.emplace_back(ctx);
+                if ((r = dmalloc(ctx, &bufs.back().p, (size_t)ncols * 8192))) return r;
+                ops[i].raw = (const uint4*)bufs.back();
+                hipLaunchKernelGGL(k_vec_expand, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, ncols, (uint4*)bufs.back());
+                const hipError_t e = hipGetLastError();
+                if (e != hipSuccess) return fail_hip(e, "k_vec_expand", __LINE__);
+            }
+            if ((r = dmalloc(ctx, &d_ops.p, ops.size() * sizeof(LeOperand))) || (r = h2d_staged(ctx, d_ops.p, ops.data(), ops.size() * sizeof(LeOperand)))) return r;
+            if ((r = dmalloc(ctx, &d_cnt.p, res.size() * 8))) return r;
+            HIPCHK(hipMemsetAsync(d_cnt.p, 0, res.size() * 8, ctx->stream));
+            // ceil(K / T) launches of about equal size, all enqueued before the one synchronisation; the first reports the valid rows
+            const size_t cap = ctx->rc_batch > 0 ? (size_t)ctx->rc_batch : (size_t)BMX_RC_BATCH_MAX;
+            const size_t npass = std::max<size_t>((K + cap - 1) / cap, 1), per = (K + npass - 1) / npass;
+            for (size_t p = 0, k0 = 0; p < npass; ++p, k0 += per) {
+                const u32 nthr = (u32)std::min(per, K - std::min(K, k0));
+                if ((r = le_counts_launch(ctx, (const LeOperand*)d_ops, (u32)nmag, ncols, sgn, plan.thr.data() + std::min(K, k0), nthr, size, not_null ? 1 : 0,
+                                          (u64*)d_cnt + 3 + NC * std::min(K, k0), p == 0 ? (u64*)d_cnt : nullptr, plane_bytes ? (u64*)d_cnt + 2 : nullptr))) return r;
+                if (launches) ++*launches;
+            }
+            HIPCHK(hipMemcpyAsync(res.data(), d_cnt.p, res.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            return BMX_OK;
+        };
+        rc = enqueue();
+        const hipError_t e = hipStreamSynchronize(ctx->stream);          // (also on an error: nothing enqueued may outlive the buffers)
+        bufs.clear(); d_ops.reset(); d_cnt.reset();
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "bmx_slice_range_counts", __LINE__);
+    }
+    auto le = [&](int cls, int64_t ref) -> uint64_t {
+        return ref == LE_NONE ? 0ull : (ref == LE_ALL ? res[(size_t)cls] : res[3 + NC * (size_t)ref + (size_t)cls]);
+    };
+    if (plane_bytes) *plane_bytes = res[2];
+    for (size_t q = 0; q < n; ++q) counts[q] = 0;
+    for (const RangeTerm& t : plan.terms) counts[t.q] += le(t.cls, t.hi) - le(t.cls, t.lo);
+    return BMX_OK;
+}
+
+extern "C" {
+
+int bmx_slice_range_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* lo, const uint64_t* hi, size_t n,
+                           uint64_t size, const bmx_vec* not_null, uint64_t* counts)
+{ ABI_TRY
+    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && (n == 0 || (lo && hi && counts)));
+    ARGCHK(!not_null || not_null->ctx == ctx);
+    for (size_t i = 0; i < nslices; ++i)
+        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
+    if (!n) return BMX_OK;
+    if (ctx->rc_batch < 0 || (ctx->rc_batch == 0 && n < RC_LOOP_BELOW)) {  // the comparison path: one pass over the planes per range
+        for (size_t q = 0; q < n; ++q) {
+            const int rc = bmx_slice_compare(ctx, slices, nslices, BMX_CMP_RANGE, lo[q], hi[q], size, not_null, nullptr, &counts[q]);
+            if (rc) return rc;
+        }
+        return BMX_OK;
+    }
+    return range_counts_impl(ctx, slices, nslices, nullptr, false, lo, hi, n, size, not_null, counts);
+ABI_END }
+
+int bmx_slice_range_counts_stat(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* lo, const uint64_t* hi, size_t n,
+                                uint64_t size, const bmx_vec* not_null, uint64_t* counts, uint64_t* plane_bytes, uint32_t* launches)
+{ ABI_TRY
+    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && n > 0 && lo && hi && counts && plane_bytes && launches);
+    ARGCHK(!not_null || not_null->ctx == ctx);
+    for (size_t i = 0; i < nslices; ++i)
+        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
+    return range_counts_impl(ctx, slices, nslices, nullptr, false, lo, hi, n, size, not_null, counts, plane_bytes, launches);
+ABI_END }
+
+int bmx_slice_range_counts_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const int64_t* lo, const int64_t* hi, size_t n,
+                                  uint64_t size, const bmx_vec* not_null, uint64_t* counts)
+{ ABI_TRY
+    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 65 && (n == 0 || (lo && hi && counts)));
+    ARGCHK(!not_null || not_null->ctx == ctx);
+    for (size_t i = 0; i < nslices; ++i)
+        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
+    if (!n) return BMX_OK;
+    if (ctx->rc_batch < 0 || (ctx->rc_batch == 0 && n < RC_LOOP_BELOW)) {
+        for (size_t q = 0; q < n; ++q) {
+            const int rc = bmx_slice_compare_signed(ctx, slices, nslices, BMX_CMP_RANGE, lo[q], hi[q], size, not_null, nullptr, &counts[q]);
+            if (rc) return rc;
+        }
+        return BMX_OK;
+    }
+    return range_counts_impl(ctx, nslices ? slices + 1 : slices, nslices ? nslices - 1 : 0, nslices ? slices[0] : nullptr, true,
+                             reinterpret_cast<const uint64_t*>(lo), reinterpret_cast<const uint64_t*>(hi), n, size, not_null, counts);
 ABI_END }
 
 } // extern "C"

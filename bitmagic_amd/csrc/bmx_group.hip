@@ -904,6 +904,39 @@ int bmx_gslice_eq_counts(bmx_group* g, const bmx_gvec* const* slices, size_t nsl
     return BMX_OK;
 ABI_END }
 
+// bmx_slice_range_counts over sharded bit-planes: every member counts over its own rows, the counts are summed
+int bmx_gslice_range_counts(bmx_group* g, const bmx_gvec* const* slices, size_t nslices, const uint64_t* lo, const uint64_t* hi, size_t n,
+                            uint64_t size, const bmx_gvec* not_null, uint64_t* counts)
+{ ABI_TRY
+    ARGCHK(g && (nslices == 0 || slices) && nslices <= 64 && (n == 0 || (lo && hi && counts)));
+    uint32_t nblocks = 0xFFFFFFFFu;
+    for (size_t i = 0; i < nslices; ++i) {
+        if (!slices[i]) continue;
+        if (slices[i]->g != g) { bmx_set_last_error("slice belongs to another group"); return BMX_ERR_BADARG; }
+        if (nblocks == 0xFFFFFFFFu) nblocks = slices[i]->nblocks;
+        else if (nblocks != slices[i]->nblocks) { bmx_set_last_error("sharded planes must cover the same block range (upload them with the same nblocks)"); return BMX_ERR_BADARG; }
+    }
+    uint64_t need = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nblocks == 0xFFFFFFFFu) nblocks = (uint32_t)need;
+    if (need != nblocks || (not_null && (not_null->g != g || not_null->nblocks != nblocks))) {
+        bmx_set_last_error("size / not-NULL vector must span the block range of the planes"); return BMX_ERR_BADARG;
+    }
+    if (!n) return BMX_OK;
+    part_ref pr = part_for(g, nblocks);
+    std::vector<std::vector<uint64_t>> part((size_t)g->n, std::vector<uint64_t>(n, 0));
+    int rc = for_each_member(g, [&](int m) -> int {
+        uint32_t blo = pr->bounds[(size_t)m], bhi = pr->bounds[(size_t)m + 1];
+        std::vector<const bmx_vec*> sl(std::max<size_t>(nslices, 1), nullptr);
+        for (size_t i = 0; i < nslices; ++i) sl[i] = slices[i] ? slices[i]->shard[(size_t)m] : nullptr;
+        return bmx_slice_range_counts(g->ctx[(size_t)m], sl.data(), nslices, lo, hi, n, shard_bits(size, blo, bhi),
+                                      not_null ? not_null->shard[(size_t)m] : nullptr, part[(size_t)m].data());
+    });
+    if (rc) return rc;
+    for (size_t q = 0; q < n; ++q) counts[q] = 0;
+    for (int m = 0; m < g->n; ++m) for (size_t q = 0; q < n; ++q) counts[q] += part[(size_t)m][q];
+    return BMX_OK;
+ABI_END }
+
 int bmx_gpipeline_destroy(bmx_group* g, bmx_gpipeline* p) { ABI_TRY if (!p) return BMX_OK; ARGCHK(g && p->g == g); return gpipeline_release(p); ABI_END }
 
 int bmx_gpipeline_create(bmx_group* g, const bmx_gvec* const* and_list, const uint32_t* and_n,

@@ -93,6 +93,7 @@ struct bmx_ctx {
     int and_rows_nt = 0;       // ... non-temporal loads of the run lists
     int and_rows_depth = 3;    // ... 1-KiB pieces in flight per wave (2 / 3 / 4 / 8)
     int ff_window = 0;         // find_first_and_sub: block columns of the FIRST launch window (each next one is 4x larger): 0 = automatic, -1 = one launch
+    int rc_batch = 0;          // bmx_slice_range_counts: thresholds per launch of k_slice_le_counts: 0 = BMX_RC_BATCH_MAX, 1..BMX_RC_BATCH_MAX = that many, -1 = one bmx_slice_compare call per range
     int or_window = 0;         // column tiles per launch of k_agg_or_gap_tiled: 0 / -1 = all in one launch (windows measured: no gain)
     int or_rows = -1;          // combine_or over >= 64 GAP-only operands through the tile directories (k_agg_or_rows, bmx_kernels7.h): -1 = when the operands average <= 4.1 chunks per GAP block, 0 = never (k_agg_or_gap_tiled), 1 = always
     int or_depth = 4;          // ... rows (operands) in flight per wave: 4 or 8

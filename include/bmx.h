@@ -88,7 +88,7 @@ int bmx_ctx_synchronize(bmx_ctx* ctx);
 /* launch-shape knobs of the counts pipeline (results never depend on them; 0 / -1 = automatic):
  * "pipe_rows" 0|8|4|2|1 (KiB of a block per work item), "pipe_unroll" 0|1|2|4|8|16, "pipe_nt" 0|1,
  * "pipe_wg" 0|64..1024 (multiples of 64; the default build carries 256, 384, 512, 640, 768), "pipe_staged" -1|0|1, "pipe_slots" 8|16,
- * "pipe_window" -1|0|N (block columns per launch), "pipe_split" -1|0|1, "direct_cols" 0..N (one-launch aggregation over small collections), "ff_window" -1|0|N (first launch window of find_first_and_sub), "pair_stream" -1|0|2|4|8 and "pair_wgs" 1..8 (shape of the streaming pairwise count kernel), "pair_loop" -1|0|1..5 and "pair_nt" 0|1 (persistent pairwise count kernel for mixed block kinds: workgroups per CU, non-temporal loads), "eq_big_shape" 0|1|2, "gap_count" -1|0|1 (counting formulation for GAP-only counts pipelines), "range_halves" 0|1 (comparison search in half-block passes), "rs_lanes" 0|2|4|8 (lanes per rank query), "rs_lines" 0|1|2 (build_rs_index also lays the vector out as rank lines: one 128-byte line per rank query), "rs_select_lines" 0|1|2 (select through the block index | the lines + octant directory | the select directory over the lines) and "rs_sdir_shift" 0|6..20 (log2 of the ones per select-directory entry; 0 = an entry per ~10 lines), "gap_pack" -1|0|1 (packed collections, see below), "eq_big" -1|0|1 (table form of bmx_slice_eq_counts), "op2_wgs" 1..8 and "op2_nt" 0..3 (streaming bit_and/or/xor/sub kernel: workgroups per CU; bit 0 / 1 = non-temporal loads / stores), "op2_loop" -1|0|1..8 (persistent bit_and/or/xor/sub kernel for mixed block kinds: workgroups per CU), "or_rows" -1|0|1 and "or_depth" 4|8 (combine_or over >= 64 sparse GAP-only operands through the vectors' tile directories: automatic | never | always; rows in flight per wave), "coll_members" -1|0|1 (lists that are SOME vectors of a prepared collection: the member directory automatic | never | whenever covered), "or_tile" 0..3, "xcd_swizzle" 0|1, "rankc_path" -1|0|1 (bmx_rank_compress / bmx_rank_decompress: automatic | ascending positions into the sorted path of bmx_vec_from_indices | whole blocks; results never depend on it), "hits_table_kb" 0..4194304 (bmx_pipeline_run_indices: KiB of the hit table a chunk of arg-groups may take).  Environment twins (BMX_PIPE_ROWS, ...) pass the same checks. */
+ * "pipe_window" -1|0|N (block columns per launch), "pipe_split" -1|0|1, "direct_cols" 0..N (one-launch aggregation over small collections), "ff_window" -1|0|N (first launch window of find_first_and_sub), "rc_batch" -1|0|1..8 (bmx_slice_range_counts: thresholds per launch; -1 = one bmx_slice_compare call per range), "pair_stream" -1|0|2|4|8 and "pair_wgs" 1..8 (shape of the streaming pairwise count kernel), "pair_loop" -1|0|1..5 and "pair_nt" 0|1 (persistent pairwise count kernel for mixed block kinds: workgroups per CU, non-temporal loads), "eq_big_shape" 0|1|2, "gap_count" -1|0|1 (counting formulation for GAP-only counts pipelines), "range_halves" 0|1 (comparison search in half-block passes), "rs_lanes" 0|2|4|8 (lanes per rank query), "rs_lines" 0|1|2 (build_rs_index also lays the vector out as rank lines: one 128-byte line per rank query), "rs_select_lines" 0|1|2 (select through the block index | the lines + octant directory | the select directory over the lines) and "rs_sdir_shift" 0|6..20 (log2 of the ones per select-directory entry; 0 = an entry per ~10 lines), "gap_pack" -1|0|1 (packed collections, see below), "eq_big" -1|0|1 (table form of bmx_slice_eq_counts), "op2_wgs" 1..8 and "op2_nt" 0..3 (streaming bit_and/or/xor/sub kernel: workgroups per CU; bit 0 / 1 = non-temporal loads / stores), "op2_loop" -1|0|1..8 (persistent bit_and/or/xor/sub kernel for mixed block kinds: workgroups per CU), "or_rows" -1|0|1 and "or_depth" 4|8 (combine_or over >= 64 sparse GAP-only operands through the vectors' tile directories: automatic | never | always; rows in flight per wave), "coll_members" -1|0|1 (lists that are SOME vectors of a prepared collection: the member directory automatic | never | whenever covered), "or_tile" 0..3, "xcd_swizzle" 0|1, "rankc_path" -1|0|1 (bmx_rank_compress / bmx_rank_decompress: automatic | ascending positions into the sorted path of bmx_vec_from_indices | whole blocks; results never depend on it), "hits_table_kb" 0..4194304 (bmx_pipeline_run_indices: KiB of the hit table a chunk of arg-groups may take).  Environment twins (BMX_PIPE_ROWS, ...) pass the same checks. */
 int bmx_ctx_set_tuning(bmx_ctx* ctx, const char* key, int value);
 /* The context keeps freed device blocks in a size-keyed cache (results of same-shaped
  * operations re-use them instead of paying hipMalloc/hipFree, which synchronises the
@@ -316,6 +316,39 @@ int bmx_slice_compare_stat(bmx_ctx* ctx, const bmx_vec* const* slices, size_t ns
  * (bit-matrix transposition + hash lookup, bmx_kernels4.h).  nslices <= 32 (else BMX_ERR_RANGE: use the pipeline form). */
 int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* values, size_t n,
                         uint64_t size, const bmx_vec* not_null, uint64_t* counts);
+
+/* a batch of range searches, counts only -- what a loop of sparse_vector_scanner::find_range / find_gt / find_le + count() computes
+ * (src/bmsparsevec_algo.h:1135-1174, 2690-2900; signed containers: find_gt_horizontal_s :1484, 3033-3160): a histogram over bin
+ * edges, quantile boundaries, COUNT(*) .. WHERE x BETWEEN a AND b for a list of intervals, the ranks of a list of values.  The
+ * reference has no batch call.  Here the n ranges become sorted distinct thresholds, and the planes are read once per
+ * BMX_RC_BATCH_MAX thresholds instead of once per range (bmx_kernels18.h: the walk of bmx_slice_compare carried for several
+ * bounds at once); every count is a difference of two "rows <= threshold" counts.
+ * counts[q] = number of rows i < size that are not NULL and hold lo[q] <= sv[i] <= hi[q]  (closed; a reversed pair is
+ * swapped, as find_range does, src/bmsparsevec_algo.h:2862).  n ranges, any overlap, any order, duplicates allowed.
+ * Row i counts iff i < size, it is not NULL (not_null == NULL: every row is valid; a row past the end of not_null is NULL) and
+ * the predicate holds in plain integer arithmetic on the value the planes spell (an operand shorter than the column reads as
+ * zeros past its end; slices[i] == NULL is a plane of zeros).  On a column that keeps the container's invariant -- a NULL row
+ * holds +0 -- this equals bmx_slice_compare[_signed](BMX_CMP_RANGE, lo[q], hi[q], ..) count-only for every q; a column that
+ * breaks the invariant is outside the contract of both entries.
+ * nslices <= 64 (signed: 65), as bmx_slice_compare; BMX_ERR_BADARG: more planes, a null context, a vector of another context,
+ * lo, hi or counts NULL with n > 0.  n == 0: BMX_OK, nothing is written.  size == 0, nslices == 0 (every value 0), a bound
+ * with a bit above every plane, hi = UINT64_MAX, lo = INT64_MIN are ordinary inputs.
+ * Tuning key "rc_batch": thresholds per launch (0 = BMX_RC_BATCH_MAX, 1..BMX_RC_BATCH_MAX = that many, -1 = one
+ * bmx_slice_compare call per range: the comparison path). */
+#define BMX_RC_BATCH_MAX 8
+int bmx_slice_range_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices,
+                           const uint64_t* lo, const uint64_t* hi, size_t n,
+                           uint64_t size, const bmx_vec* not_null, uint64_t* counts);
+/* bmx_slice_range_counts always through the batch kernel (whatever "rc_batch" and n say; n > 0), reporting what it enqueued:
+ * the launches over the planes and the plane / not-NULL bytes they loaded -- a piece's walk stops once no row is "equal so
+ * far" for any threshold of its launch -- as bmx_slice_compare_stat does for one search (benchmark reports divide by them) */
+int bmx_slice_range_counts_stat(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices,
+                                const uint64_t* lo, const uint64_t* hi, size_t n,
+                                uint64_t size, const bmx_vec* not_null, uint64_t* counts, uint64_t* plane_bytes, uint32_t* launches);
+/* signed containers: slices[0] is the sign plane, slices[1..] the magnitude (s2u, src/bmbmatrix.h:2536); signed bounds */
+int bmx_slice_range_counts_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices,
+                                  const int64_t* lo, const int64_t* hi, size_t n,
+                                  uint64_t size, const bmx_vec* not_null, uint64_t* counts);
 
 /* ---- which rows differ between two resident columns (bmx_kernels17.h) ----
  * A column is what bmx_slice_compare takes: a[i] = device vector of bit-plane i or NULL, na planes, size_a rows, not_null_a or
@@ -627,6 +660,11 @@ int bmx_gslice_compare(bmx_group* g, const bmx_gvec* const* slices, size_t nslic
 /* bmx_slice_eq_counts over sharded bit-planes (same conditions as bmx_gslice_compare) */
 int bmx_gslice_eq_counts(bmx_group* g, const bmx_gvec* const* slices, size_t nslices, const uint64_t* values, size_t n,
                          uint64_t size, const bmx_gvec* not_null, uint64_t* counts);
+/* bmx_slice_range_counts over sharded planes: every member counts over its rows, the counts are summed (as bmx_gslice_eq_counts;
+ * same conditions as bmx_gslice_compare; a loop of find_range + count(), src/bmsparsevec_algo.h:2862) */
+int bmx_gslice_range_counts(bmx_group* g, const bmx_gvec* const* slices, size_t nslices,
+                            const uint64_t* lo, const uint64_t* hi, size_t n,
+                            uint64_t size, const bmx_gvec* not_null, uint64_t* counts);
 /* aggregator::pipeline + combine_and_sub(pipe), counts only (src/bmaggregator.h:1292-1399): member m runs the
  * pipeline over its shard of every operand, counts_out[g] = sum over the members */
 int bmx_gpipeline_create(bmx_group* g,

@@ -364,6 +364,9 @@ template <> struct scanner_traits<gbvector> {
     static int eq_counts(ctx_type& g, const handle_type* const* h, size_t n, const uint64_t* values, size_t nv, uint64_t size,
                          const handle_type* nn, uint64_t* counts)
     { return bmx_gslice_eq_counts(g.handle(), h, n, values, nv, size, nn, counts); }
+    static int range_counts(ctx_type& g, const handle_type* const* h, size_t n, const uint64_t* lo, const uint64_t* hi, size_t nr, uint64_t size,
+                            const handle_type* nn, uint64_t* counts)
+    { return bmx_gslice_range_counts(g.handle(), h, n, lo, hi, nr, size, nn, counts); }
 };
 typedef basic_slice_scanner<gbvector> gslice_scanner;
 

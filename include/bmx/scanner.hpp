@@ -17,6 +17,10 @@
 //   find_gt / find_ge / find_lt / find_le / find_range             slice_scanner::find_gt(value, bv_out) ...
 //        :1135-1174 -> :2690-2880, find_gt_horizontal_u :2914         ONE pass over the planes (bmx_slice_compare,
 //   find_zero :2290, find_nonzero :4464, find_eq(sv, 0, ..) :4366     bmx_kernels4.h) instead of a chain of vector ops
+//   a loop of find_range(sv, from, to, bv) :2862 + bv.count()     slice_scanner::find_range_counts(lo, hi, n, counts)
+//        (histograms, quantile boundaries, BETWEEN lists)         slice_scanner::histogram(edges, n_edges, counts)
+//                                                                    the planes are read once per 8 distinct thresholds,
+//                                                                    not once per range (bmx_slice_range_counts, bmx_kernels18.h)
 //
 // The slices stay resident in HBM; a batch of searches is ONE counts-only pipeline launch (the
 // LDS-staged kernel when many groups share the slices).  The container
@@ -40,6 +44,9 @@ template <> struct scanner_traits<bvector> {
     static int eq_counts(ctx_type& c, const handle_type* const* h, size_t n, const uint64_t* values, size_t nv, uint64_t size,
                          const handle_type* nn, uint64_t* counts)
     { return bmx_slice_eq_counts(c.handle(), h, n, values, nv, size, nn, counts); }
+    static int range_counts(ctx_type& c, const handle_type* const* h, size_t n, const uint64_t* lo, const uint64_t* hi, size_t nr, uint64_t size,
+                            const handle_type* nn, uint64_t* counts)
+    { return bmx_slice_range_counts(c.handle(), h, n, lo, hi, nr, size, nn, counts); }
 };
 
 /// BV = bmx::bvector (one device, `slice_scanner`) or bmx::gbvector (a device group, `gslice_scanner` in group.hpp:
@@ -50,6 +57,7 @@ class basic_slice_scanner {
     typedef typename traits::ctx_type ctx_type;
     typedef BV bvector;                     // (the method bodies below are written against this name)
 public:
+    typedef uint64_t value_type;
     explicit basic_slice_scanner(ctx_type& ctx) : ctx_(&ctx), agg_(ctx) {}
 
     /// slice i holds bit i of every element; nullptr = the plane does not exist (sv.get_slice(i) == 0).
@@ -135,6 +143,32 @@ public:
         pipe.complete();
         agg_.combine_and_sub(pipe);
         for (size_t q = 0; q < n; ++q) if (slot[q] != ~size_t(0)) counts[q] = pipe.get_bv_count_vector()[slot[q]];
+    }
+
+    /// counts[q] = not-NULL rows with lo[q] <= value <= hi[q] (closed; a reversed pair is swapped, as find_range does, :2862):
+    /// a loop of find_range + count() in one pass over the planes per 8 distinct thresholds (bmx_slice_range_counts)
+    void find_range_counts(const value_type* lo, const value_type* hi, size_t n, uint64_t* counts)
+    {
+        typedef typename traits::handle_type handle_type;
+        std::vector<const handle_type*> h(slices_.size() ? slices_.size() : 1, nullptr);
+        for (size_t i = 0; i < slices_.size(); ++i) h[i] = slices_[i] ? slices_[i]->handle() : nullptr;
+        check(traits::range_counts(*ctx_, h.data(), slices_.size(), lo, hi, n, size_,
+                                   (not_null_ && !not_null_->empty_handle()) ? not_null_->handle() : nullptr, counts));
+    }
+
+    /// n_edges - 1 bins [edges[k], edges[k + 1]) over ascending edges; a bin whose edges are equal is empty (0)
+    void histogram(const value_type* edges, size_t n_edges, uint64_t* counts)
+    {
+        if (n_edges < 2) return;
+        std::vector<value_type> lo, hi; std::vector<size_t> bin;
+        for (size_t k = 0; k + 1 < n_edges; ++k) {
+            if (edges[k + 1] < edges[k]) throw error(BMX_ERR_BADARG, "histogram edges must ascend");
+            counts[k] = 0;
+            if (edges[k] < edges[k + 1]) { lo.push_back(edges[k]); hi.push_back(edges[k + 1] - 1); bin.push_back(k); }
+        }
+        std::vector<uint64_t> c(bin.size(), 0);
+        if (!bin.empty()) find_range_counts(lo.data(), hi.data(), bin.size(), c.data());
+        for (size_t i = 0; i < bin.size(); ++i) counts[bin[i]] = c[i];
     }
 
     /// a batch of find_eq(sv, value, bi) (:1096): ids[offsets[q] .. offsets[q + 1]) = the rows equal to values[q], ascending.  One
