@@ -53,7 +53,8 @@ __all__ = ["context", "bvector", "aggregator", "slice_scanner", "rs_index", "ran
            "COUNT_AND", "COUNT_XOR", "COUNT_OR", "COUNT_SUB_AB", "COUNT_SUB_BA", "COUNT_A", "COUNT_B", "BmxError", "simd_version", "device_count", "agg_run_options",
            "agg_opt_only_counts", "agg_opt_bvect_and_counts", "agg_opt_disable_bvects_and_counts",
            "BM_UNSORTED", "BM_SORTED", "BM_SORTED_UNIFORM", "BM_UNKNOWN",
-           "sparse_vector_find_mismatch", "sparse_vector_count_mismatch", "sparse_vector_find_first_mismatch", "USE_NULL", "NO_NULL"]
+           "sparse_vector_find_mismatch", "sparse_vector_count_mismatch", "sparse_vector_find_first_mismatch", "USE_NULL", "NO_NULL",
+           "set2set_11_transform"]
 
 
 def simd_version() -> int:
@@ -1272,6 +1273,82 @@ class slice_scanner:
         if bins:
             out[bins] = self.find_range_counts([e[k] for k in bins], [e[k + 1] - 1 for k in bins])
         return out
+
+    # ---- reading values out of the planes (include/bmx.h "reading values out of resident planes") ----
+    def _values_args(self, mask: "bvector | None"):
+        if type(self) is not slice_scanner:
+            raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "values / remap: a slice_scanner of one device expected (no group form)")
+        if mask is not None and mask.ctx is not self.ctx:
+            raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "the selector lives in another context")
+        arr = (C.c_void_p * max(len(self.slices), 1))()
+        for i, p in enumerate(self.slices):
+            arr[i] = p._h if p is not None else None
+        return [self.ctx._h, arr, len(self.slices), self.size(), self.not_null._h if self.not_null is not None else None,
+                mask._h if mask is not None else None]
+
+    def value_width(self) -> int:
+        """bytes per entry of the value lists: 4 up to 32 planes, 8 beyond"""
+        return 4 if len(self.slices) <= 32 else 8
+
+    def values(self, mask: "bvector | None" = None, rows: bool = False):
+        """the values of the rows of `mask` (None: every row) that are not NULL and below size(), ascending by row -- what
+        sv.gather delivers for the rows set2set_11_transform::remap enumerates (src/bmsparsevec_algo.h:2170-2204); rows=True:
+        -> (values, row ids).  A signed scanner's patterns are converted to integers (int64); an unsigned one gives uint32 up to
+        32 planes and uint64 beyond (bmx_slice_values)"""
+        args = self._values_args(mask)
+        w = self.value_width()
+        dt = np.uint32 if w == 4 else np.uint64
+        n = C.c_uint64()
+        rc = lib().bmx_slice_values(*args, w, None, None, 0, C.byref(n))                     # (the number of rows first)
+        if rc != 0 and not (rc == _ffi.ERR_RANGE and n.value):
+            check(rc)
+        vals, ids = np.zeros(n.value, dt), (np.zeros(n.value, dt) if rows else None)
+        if n.value:
+            check(lib().bmx_slice_values(*args, w, _ptr(vals), _ptr(ids) if rows else None, n.value, C.byref(n)))
+        if self.signed:                                                   # u2s (src/bmbmatrix.h:2551)
+            u = vals.astype(np.uint64)
+            vals = np.where(u & np.uint64(1), ~(u >> np.uint64(1)), u >> np.uint64(1)).astype(np.uint64).view(np.int64)
+        return (vals, ids) if rows else vals
+
+    def values_dev(self, values_ptr: int, cap: int, mask: "bvector | None" = None, rows_ptr: int | None = None, width: int | None = None) -> int:
+        """bmx_slice_values_dev: the bit patterns (never converted) into device memory at values_ptr, room for cap entries of
+        `width` bytes (default value_width()), the row ids to rows_ptr when given; the buffers and the operands must be ready
+        for the context's stream.  -> the number of selected rows; more than cap raises BmxError(RANGE) and writes nothing"""
+        n = C.c_uint64()
+        check(lib().bmx_slice_values_dev(*self._values_args(mask), int(width or self.value_width()), C.c_void_p(values_ptr) if values_ptr else None,
+                                         C.c_void_p(rows_ptr) if rows_ptr else None, int(cap), C.byref(n)))
+        return int(n.value)
+
+
+class set2set_11_transform:
+    """bm::set2set_11_transform<SV> (src/bmsparsevec_algo.h:1890-2205): the image of a row set under a relation column,
+    { sv[i] : i in bv_in, sv[i] not NULL }, built on the device (bmx_slice_remap).  The column is a slice_scanner (unsigned);
+    M:1 relations are ordinary input."""
+
+    def __init__(self, ctx: context):
+        self.ctx, self._sv, self.n_rows = ctx, None, 0
+
+    def attach_sv(self, scanner: "slice_scanner | None", compute_stats: bool = False) -> None:
+        """attach_sv(sv_brel, compute_stats) :2047 (None detaches); compute_stats is accepted and ignored: no pass needs it"""
+        self._sv = scanner
+
+    def remap(self, bv_in: "bvector | None", scanner: "slice_scanner | None" = None, nbits: int = 0, optimize: bool = True) -> bvector:
+        """remap(bv_in, sv_brel, bv_out) :2096 / remap(bv_in, bv_out) :2114 with the attached column -> bv_out, a vector of
+        max(nbits, largest value + 1) bits; n_rows = rows that were translated.  bv_in None: every row"""
+        sv = scanner if scanner is not None else self._sv
+        if sv is None:
+            raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "remap without a column: pass one or attach_sv first")
+        if sv.signed:
+            raise BmxError(_ffi.ERR_BADARG, "Invalid argument", "remap over a signed column: positions cannot be negative")
+        h, n = C.c_void_p(), C.c_uint64()
+        check(lib().bmx_slice_remap(*sv._values_args(bv_in), int(nbits), int(bool(optimize)), C.byref(h), C.byref(n)))
+        self.n_rows = int(n.value)
+        return bvector(self.ctx, h)
+
+    def run(self, bv_in: "bvector | None", scanner: "slice_scanner", nbits: int = 0, optimize: bool = True) -> bvector:
+        """run(bv_in, sv_brel, bv_out) :1960"""
+        return self.remap(bv_in, scanner, nbits, optimize)
+
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -101,6 +101,9 @@ def lib() -> C.CDLL:
         "bmx_slice_range_counts_signed": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp]),
         "bmx_slice_mismatch": (i32, [vp, P(vp), C.c_size_t, u64, vp, P(vp), C.c_size_t, u64, vp, i32, P(vp), P(u64)]),
         "bmx_slice_first_mismatch": (i32, [vp, P(vp), C.c_size_t, u64, vp, P(vp), C.c_size_t, u64, vp, i32, P(i32), P(u64)]),
+        "bmx_slice_values": (i32, [vp, P(vp), C.c_size_t, u64, vp, vp, i32, vp, vp, u64, P(u64)]),
+        "bmx_slice_values_dev": (i32, [vp, P(vp), C.c_size_t, u64, vp, vp, i32, vp, vp, u64, P(u64)]),
+        "bmx_slice_remap": (i32, [vp, P(vp), C.c_size_t, u64, vp, vp, u64, i32, P(vp), P(u64)]),
         "bmx_collection_prepare": (i32, [vp, P(vp), C.c_size_t, i32]),
         "bmx_ctx_pack_stats": (i32, [vp, P(u32), P(u64), P(C.c_float)]),
         "bmx_ctx_pack_run_bytes": (i32, [vp, P(u64)]),

@@ -21,6 +21,7 @@
 #include "bmx_kernels16.h"
 #include "bmx_kernels17.h"
 #include "bmx_kernels18.h"
+#include "bmx_kernels19.h"
 
 #include <algorithm>
 #include <atomic>
@@ -4148,6 +4149,120 @@ int bmx_slice_first_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, u
                              int* found, uint64_t* idx)
 { ABI_TRY
     return slice_mismatch_impl(ctx, a, na, size_a, not_null_a, b, nb, size_b, not_null_b, null_proc, true, nullptr, nullptr, found, idx);
+ABI_END }
+
+// ---- the values of the selected rows, and the image of a row set under the column (bmx_kernels19.h) ----
+// Counting half: the operand table (planes, not-NULL vector, selector), the selected rows per block column, their exclusive
+// starts and the total, read on the host (one synchronise).  The tables stay for the emit half.
+struct SliceValues {
+    OperandTable ops; DevBuf d_tab, d_cnt, d_start;
+    uint32_t ncols = 0, P = 0; uint64_t size = 0, total = 0;
+    explicit SliceValues(bmx_ctx* ctx) : d_tab(ctx), d_cnt(ctx), d_start(ctx) {}
+};
+static int slice_values_count(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                              const bmx_vec* bv_in, SliceValues* sv)
+{
+    int rc;
+    uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    sv->ncols = (uint32_t)nblocks64; sv->P = (uint32_t)nslices; sv->size = size; sv->total = 0;
+    std::vector<const bmx_vec*> list(nslices + 2, nullptr);
+    for (size_t i = 0; i < nslices; ++i) list[i] = slices[i];
+    list[nslices] = not_null; list[nslices + 1] = bv_in;
+    if ((rc = operand_list(ctx, list.data(), list.size(), nullptr, 0, true, &sv->ops))) return rc;
+    if (!sv->ncols) return BMX_OK;
+    if ((rc = direct_table(ctx, &sv->ops, sv->d_tab)) || (rc = dmalloc(ctx, &sv->d_cnt.p, (size_t)sv->ncols * 4)) ||
+        (rc = dmalloc(ctx, &sv->d_start.p, (size_t)sv->ncols * 8))) return rc;
+    hipLaunchKernelGGL(k_slice_sel_counts, dim3((sv->ncols + 3) / 4), dim3(256), 0, ctx->stream, sv->ops.d_descs, sv->ops.d_nblk, sv->P,
+                       sv->ncols, size, (u32*)sv->d_cnt);
+    hipLaunchKernelGGL(k_pipe_hit_scan, dim3(1), dim3(256), 0, ctx->stream, (const u32*)sv->d_cnt, sv->ncols, (u64*)sv->d_start, ctx->d_small);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    sv->total = ctx->h_small[0];
+    return BMX_OK;
+}
+// Emit half (enqueued, not waited for): d_values / d_rows hold sv.total entries of `width` bytes; d_rows may be null
+static int slice_values_emit(bmx_ctx* ctx, const SliceValues& sv, int width, void* d_values, void* d_rows)
+{
+    const dim3 grid((sv.ncols + 3) / 4);
+    if (width == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_values<2, u64>), grid, dim3(256), 0, ctx->stream, sv.ops.d_descs, sv.ops.d_nblk, sv.P,
+                                       sv.ncols, sv.size, (const u32*)sv.d_cnt, (const u64*)sv.d_start, (u64*)d_values, (u64*)d_rows, sv.total);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_values<1, u32>), grid, dim3(256), 0, ctx->stream, sv.ops.d_descs, sv.ops.d_nblk, sv.P,
+                            sv.ncols, sv.size, (const u32*)sv.d_cnt, (const u64*)sv.d_start, (u32*)d_values, (u32*)d_rows, sv.total);
+    KCHK();
+    return BMX_OK;
+}
+static int slice_values_args(const bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int width)
+{
+    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && (width == 4 || width == 8));
+    if (width == 4 && nslices > 32) { g_last_error = "more than 32 planes do not fit 32-bit values: use width 8"; return BMX_ERR_BADARG; }
+    return BMX_OK;
+}
+
+static int slice_values_impl(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                             const bmx_vec* bv_in, int width, void* values, void* rows, bool host, uint64_t cap, uint64_t* n)
+{
+    int rc = slice_values_args(ctx, slices, nslices, width); if (rc) return rc;
+    ARGCHK(n && (cap == 0 || values));
+    *n = 0;
+    if ((rc = set_dev(ctx))) return rc;
+    if (rows && width == 4 && size > (1ull << 32)) { g_last_error = "32-bit row ids cannot address this column: use width 8"; return BMX_ERR_RANGE; }
+    SliceValues sv(ctx);
+    if ((rc = slice_values_count(ctx, slices, nslices, size, not_null, bv_in, &sv))) return rc;
+    *n = sv.total;
+    if (sv.total > cap) { g_last_error = "output buffer too small for the values (n holds the number needed)"; return BMX_ERR_RANGE; }
+    if (!sv.total) return BMX_OK;
+    const size_t bytes = (size_t)sv.total * (size_t)width;
+    DevBuf h_val(ctx), h_rows(ctx);
+    if (host && ((rc = dmalloc(ctx, &h_val.p, bytes)) || (rows && (rc = dmalloc(ctx, &h_rows.p, bytes))))) return rc;
+    void* d_val = host ? h_val.p : values;
+    void* d_rows = host ? h_rows.p : rows;
+    if ((rc = slice_values_emit(ctx, sv, width, d_val, d_rows))) return rc;
+    if (host) {
+        HIPCHK(hipMemcpyAsync(values, d_val, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (rows) HIPCHK(hipMemcpyAsync(rows, d_rows, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return BMX_OK;
+}
+
+int bmx_slice_values(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                     const bmx_vec* bv_in, int width, void* values, void* rows, uint64_t cap, uint64_t* n)
+{ ABI_TRY
+    return slice_values_impl(ctx, slices, nslices, size, not_null, bv_in, width, values, rows, true, cap, n);
+ABI_END }
+
+int bmx_slice_values_dev(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                         const bmx_vec* bv_in, int width, void* d_values, void* d_rows, uint64_t cap, uint64_t* n)
+{ ABI_TRY
+    return slice_values_impl(ctx, slices, nslices, size, not_null, bv_in, width, d_values, d_rows, false, cap, n);
+ABI_END }
+
+// set2set_11_transform::remap (src/bmsparsevec_algo.h:2114-2205): the values of the selected rows into a transient list, then
+// the vector of that list (ids_import: unsorted, duplicates, size rule, optimize rule).  No list crosses to the host.
+int bmx_slice_remap(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                    const bmx_vec* bv_in, uint64_t nbits_out, int optimize, bmx_vec** result, uint64_t* n_rows)
+{ ABI_TRY
+    ARGCHK(result);
+    *result = nullptr;
+    if (n_rows) *n_rows = 0;
+    const int width = nslices > 32 ? 8 : 4;
+    int rc = slice_values_args(ctx, slices, nslices, width); if (rc) return rc;
+    if (nbits_out > (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    if ((rc = set_dev(ctx))) return rc;
+    DevBuf d_val(ctx);
+    uint64_t n = 0;
+    {
+        SliceValues sv(ctx);
+        if ((rc = slice_values_count(ctx, slices, nslices, size, not_null, bv_in, &sv))) return rc;
+        n = sv.total;
+        if (n > 0xFFFFFFFFull) { g_last_error = "more than 2^32 - 1 selected rows in one call"; return BMX_ERR_RANGE; }
+        if (n && ((rc = dmalloc(ctx, &d_val.p, (size_t)n * (size_t)width)) || (rc = slice_values_emit(ctx, sv, width, d_val.p, nullptr)))) return rc;
+    }                                                       // (the tables are pooled: the next user is enqueued behind the emit)
+    if ((rc = ids_import(ctx, d_val.p, width, n, nbits_out, 0u, 0xFFFFFFFFu, optimize, result))) return rc;
+    if (n_rows) *n_rows = n;
+    return BMX_OK;
 ABI_END }
 
 // counts[q] = rows equal to values[q]: one pass over the planes whatever the number of queries (k_slice_eq_counts:

@@ -387,6 +387,49 @@ int bmx_slice_first_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, u
                              const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* not_null_b, int null_proc,
                              int* found, uint64_t* idx);
 
+/* ---- reading values out of resident planes: the selected rows' values, and a row set's image under the column (bmx_kernels19.h) ----
+ * A column is what bmx_slice_compare takes (slices[i] = plane i or NULL, nslices planes, size rows, not_null or NULL); bv_in is
+ * the selector, NULL = every row.  The selected rows are
+ *     S = ones(bv_in) & ones(not_null) & [0, size)
+ * the rows set2set_11_transform::remap enumerates (bv_product_ = bv_in & *bv_non_null, src/bmsparsevec_algo.h:2134-2141; without a
+ * not-NULL vector bv_in itself, :2142-2144).  A vector shorter than the column reads as zeros past its end; selector bits at or
+ * beyond size are DROPPED, also those inside the block that holds size: the reference hands them to sv.gather (:2181), which has
+ * no defined result past the end of the vector -- a stated choice, not the reference's behaviour.
+ *
+ * bmx_slice_values[_dev]: values[k] = the bit pattern the planes hold at the k-th row of S in ascending row order,
+ *   sum over p of bit(plane p, row) << p -- what sv.gather(buffer, idx, n, BM_SORTED_UNIFORM) delivers per window (:2181, :2195,
+ *   :2202); an absent plane contributes zeros.  A signed container's patterns are its s2u patterns (sign in bit 0,
+ *   src/bmbmatrix.h:2536): the caller converts.  rows, when not NULL, receives the row ids (the enumerator's *en, :2173).  Both lists
+ *   are written at `width` bytes per entry (4 or 8).  Without a not-NULL vector a row whose planes are all clear has the value 0
+ *   like any other (:2142-2163: the reference without statistics enumerates bv_in as it is).
+ *   Capacity, the protocol of bmx_vec_to_indices: *n = number of selected rows; *n > cap: nothing is written, BMX_ERR_RANGE.
+ *   bmx_slice_values takes host buffers; bmx_slice_values_dev takes device buffers and operands that are ready on the context's
+ *   stream, and returns when the lists are complete.
+ *   BMX_ERR_BADARG: null context or n, width not 4 / 8, width 4 with nslices > 32, nslices > 64, a vector of another context,
+ *   values NULL with cap > 0.  BMX_ERR_RANGE also: rows at width 4 for a column of more than 2^32 rows.
+ *
+ * bmx_slice_remap = set2set_11_transform<SV>::remap(bv_in, sv_brel, bv_out) (:2096-2205): *result = the set { sv[i] : i in S } as
+ *   a vector -- bv_out.set(buffer, n) of every gathered window (:2182, :2196, :2203) -- built on the device: the values of
+ *   bmx_slice_values_dev go into a transient list and through bmx_vec_from_indices_dev(BMX_UNSORTED); no list crosses to the
+ *   host.  M:1 relations (duplicate values) are ordinary input.  Without a not-NULL vector a selected row with all planes clear
+ *   sets bit 0 of the image, as the reference does when it has no statistics (:2142-2163; with statistics it sets the same bit
+ *   through bv_zero_, :2149-2160).
+ *   Size: the image has max(nbits_out, largest value + 1) bits (the size rule of bmx_vec_from_indices; the reference's bv_out
+ *   has the full address range).  optimize: as bmx_vec_from_indices.  An empty selection gives an all-NULL vector of nbits_out
+ *   bits (bv_out.clear(), :2119).  *n_rows (may be NULL) = rows that were translated = count(S).
+ *   The values are positions, so the column must be an unsigned container's.
+ *   BMX_ERR_BADARG: as above, and result NULL.  BMX_ERR_RANGE, with nothing left allocated: the limits of
+ *   bmx_vec_from_indices_dev -- a value at or beyond 2^36 (2^20 blocks), nbits_out beyond it, 2^32 or more selected rows. */
+int bmx_slice_values(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                     const bmx_vec* bv_in /* or NULL: every row */, int width, void* values, void* rows /* or NULL */,
+                     uint64_t cap, uint64_t* n);
+int bmx_slice_values_dev(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                         const bmx_vec* bv_in /* or NULL */, int width, void* d_values, void* d_rows /* or NULL */,
+                         uint64_t cap, uint64_t* n);
+int bmx_slice_remap(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                    const bmx_vec* bv_in /* or NULL */, uint64_t nbits_out, int optimize, bmx_vec** result,
+                    uint64_t* n_rows /* or NULL */);
+
 /* ---- packed collections: a column-major copy of the GAP run lists of a SET of vectors (bmx_kernels6.h, bmx_kernels8.h) ----
  * Vectors are immutable and device-resident, so the library owns their layout.  combine_or / combine_and / combine_and_sub
  * and pipelines over many operands made of GAP (+ NULL / FULL) blocks read thousands of separate slabs in small pieces

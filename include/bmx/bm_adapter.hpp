@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 #include <unordered_map>
+#include <type_traits>
 #include <vector>
 
 #include "bvector.hpp"
@@ -562,6 +563,27 @@ bool sparse_vector_find_first_mismatch(context& ctx, const SV& sv1, const SV& sv
     if (!sparse_vector_find_first_mismatch(a, b, idx, null_proc == bm::use_null ? use_null : no_null)) return false;
     midx = (typename SV::size_type)idx;
     return true;
+}
+
+/// bm::set2set_11_transform<SV>::remap(bv_in, sv_brel, bv_out) (src/bmsparsevec_algo.h:2096) over HOST containers, the reference's
+/// argument order behind the context: the column's planes and bv_in are uploaded, the image is built on the device
+/// (bmx::set2set_11_transform, bmx/sv_algo.hpp) and installed into the host vector.  Rows of bv_in at or beyond sv_brel.size()
+/// are dropped (include/bmx.h).  A signed container is refused: positions cannot be negative.
+template <class SV>
+void set2set_11_remap(context& ctx, const typename SV::bvector_type& bv_in, const SV& sv_brel, typename SV::bvector_type& bv_out)
+{
+    if (std::is_signed<typename SV::value_type>::value) throw error(BMX_ERR_BADARG, "set2set_11_transform over a signed container");
+    bv_out.clear();
+    if (sv_brel.empty()) return;                                         // :2121
+    std::vector<bvector> store; std::vector<const bvector*> sl; const bvector* nn = nullptr;
+    upload_slices(sv_brel, ctx, store, sl, &nn);
+    slice_scanner col(ctx);
+    col.bind(sl, sv_brel.size(), nn);
+    bvector d_in(ctx), d_out(ctx);
+    upload(bv_in, d_in);
+    set2set_11_transform t;
+    t.remap(d_in, col, d_out);
+    download(d_out, bv_out);
 }
 
 } // namespace bmx

@@ -21,6 +21,8 @@
 //        (histograms, quantile boundaries, BETWEEN lists)         slice_scanner::histogram(edges, n_edges, counts)
 //                                                                    the planes are read once per 8 distinct thresholds,
 //                                                                    not once per range (bmx_slice_range_counts, bmx_kernels18.h)
+//   sv.gather(buf, idx, n, BM_SORTED_UNIFORM) over the rows of a    slice_scanner::values(rows_mask, values, rows)
+//        bit-vector (set2set_11_transform::remap :2170-2204)          one device only (bmx_slice_values, bmx_kernels19.h)
 //
 // The slices stay resident in HBM; a batch of searches is ONE counts-only pipeline launch (the
 // LDS-staged kernel when many groups share the slices).  The container
@@ -47,6 +49,10 @@ template <> struct scanner_traits<bvector> {
     static int range_counts(ctx_type& c, const handle_type* const* h, size_t n, const uint64_t* lo, const uint64_t* hi, size_t nr, uint64_t size,
                             const handle_type* nn, uint64_t* counts)
     { return bmx_slice_range_counts(c.handle(), h, n, lo, hi, nr, size, nn, counts); }
+    /// (one device only: a group has no twin of this entry)
+    static int values(ctx_type& c, const handle_type* const* h, size_t n, uint64_t size, const handle_type* nn, const handle_type* sel,
+                      int width, void* values, void* rows, uint64_t cap, uint64_t* cnt)
+    { return bmx_slice_values(c.handle(), h, n, size, nn, sel, width, values, rows, cap, cnt); }
 };
 
 /// BV = bmx::bvector (one device, `slice_scanner`) or bmx::gbvector (a device group, `gslice_scanner` in group.hpp:
@@ -74,6 +80,33 @@ public:
     const std::vector<const bvector*>& slices() const noexcept { return slices_; }
     const bvector* not_null() const noexcept { return (not_null_ && !not_null_->empty_handle()) ? not_null_ : nullptr; }
     ctx_type& ctx() const noexcept { return *ctx_; }
+
+    /// the planes are those of a signed container (slices[0] = the sign, s2u, src/bmbmatrix.h:2536): values() converts the
+    /// patterns, set2set_11_transform refuses the column.  The searches above and below take what their comments say.
+    void set_signed(bool on) noexcept { signed_ = on; }
+    bool is_signed() const noexcept { return signed_; }
+
+    /// the values of the rows of rows_mask (nullptr: every row) that are not NULL and below size(), ascending by row -- what
+    /// sv.gather delivers for the rows set2set_11_transform::remap enumerates (src/bmsparsevec_algo.h:2170-2204) -- and, when
+    /// rows is given, their row ids (bmx_slice_values).  A signed scanner's patterns are converted to integers (u2s), held as
+    /// two's complement in the uint64_t.
+    void values(const bvector* rows_mask, std::vector<uint64_t>& values, std::vector<size_type>* rows = nullptr) const
+    {
+        typedef typename traits::handle_type handle_type;
+        std::vector<const handle_type*> h(slices_.size() ? slices_.size() : 1, nullptr);
+        for (size_t i = 0; i < slices_.size(); ++i) h[i] = (slices_[i] && !slices_[i]->empty_handle()) ? slices_[i]->handle() : nullptr;
+        const handle_type* nn = (not_null_ && !not_null_->empty_handle()) ? not_null_->handle() : nullptr;
+        const handle_type* sel = nullptr;
+        values.clear(); if (rows) rows->clear();
+        if (rows_mask) { if (rows_mask->empty_handle()) return; sel = rows_mask->handle(); }      // (a vector without content selects nothing)
+        uint64_t n = 0;
+        int rc = traits::values(*ctx_, h.data(), slices_.size(), size_, nn, sel, 8, nullptr, nullptr, 0, &n);   // (the number of rows first)
+        if (rc != BMX_OK && !(rc == BMX_ERR_RANGE && n)) check(rc);
+        if (!n) return;
+        values.resize(n); if (rows) rows->resize(n);
+        check(traits::values(*ctx_, h.data(), slices_.size(), size_, nn, sel, 8, values.data(), rows ? rows->data() : nullptr, n, &n));
+        if (signed_) for (size_t i = 0; i < values.size(); ++i) { const uint64_t u = values[i]; values[i] = (u & 1u) ? ~(u >> 1) : (u >> 1); }
+    }
 
     // ---- comparison searches (unsigned values): one pass over the planes ----
     void find_gt(uint64_t value, bvector& bv_out) { compare(BMX_CMP_GT, value, 0, &bv_out); }            // :2690
@@ -230,6 +263,7 @@ private:
     std::vector<const bvector*> slices_;
     size_type size_ = 0;
     const bvector* not_null_ = nullptr;
+    bool signed_ = false;
 };
 
 typedef basic_slice_scanner<bvector> slice_scanner;
