@@ -88,10 +88,13 @@ static int dmalloc_injected(bmx_ctx* ctx)
     g_last_error = "injected device allocation failure"; return BMX_ERR_BADALLOC;
 }
 
+// Granules of the device pool: 256 bytes, from 64 KiB on one bit-block (8 KiB), from 2 MiB on 2 MiB.  (The middle granule was
+// 64 KiB: a result slab compacted from 16 slots to 13 live blocks -- bit_slab_settle -- then occupied the two granules it had
+// before, a copy that gave nothing back; a request is served from the pool within 25 % of its size either way.)
 static size_t pool_round(size_t bytes)
 {
     if (bytes < 256) bytes = 256;
-    size_t g = bytes >= (2u << 20) ? (2u << 20) : (bytes >= (64u << 10) ? (64u << 10) : 256u);
+    size_t g = bytes >= (2u << 20) ? (2u << 20) : (bytes >= (64u << 10) ? (8u << 10) : 256u);
     return (bytes + g - 1) / g * g;
 }
 

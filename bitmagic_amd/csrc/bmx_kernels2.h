@@ -89,6 +89,9 @@ __device__ __forceinline__ u32 store_result_mode(const Blk& acc, u32 nb, u32 mod
     else if (mode & (ST_FORCE_GAP | ST_OPT)) {
         kind = (runs == 1u) ? (first ? K_FULL : K_NULL) : (runs < 1276u ? K_GAP : K_BIT);
         if ((mode & ST_GAP_RESULT) && runs == 1u && first) kind = K_GAP;      // 1-run GAP block [hdr, 65535]
+        // ... and asks gap_calc_level for len = the run count, where optimize_bit_block and a copy (clone_gap_block(blk, res),
+        // :838: gap_length = len + 1) compare one less: a GAP x GAP result of exactly 1,276 runs is still a GAP block
+        if ((mode & ST_GAP_RESULT) && runs == 1276u) kind = K_GAP;
     } else {
         kind = K_BIT;
         if ((mode & ST_TEST_ZERO) && runs == 1u && !first) kind = K_NULL;

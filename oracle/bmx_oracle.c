@@ -828,6 +828,14 @@ static void clone_block(bmo_vec* t, uint32_t nb, const bmo_vec* s, int invert)
         if (one) t->kind[nb] = BMO_FULL;
         return;
     }
+    /* clone_gap_block(gap_block, gap_res), src/bmblocks.h:838-860: the level is asked for gap_length = len + 1 words, so the
+     * block of 1,276 runs -- which only a GAP x GAP result can be (store_gap_result asks for len) -- "mutates" into a bit-block */
+    if (gap_calc_level(gap_len(g) + 1u) < 0) {
+        uint32_t* q = alloc_bit_block();
+        bmo_gap_convert_to_bitset(q, g);
+        if (invert) for (unsigned i = 0; i < BMO_BLOCK_WORDS; ++i) q[i] = ~q[i];
+        t->blk[nb] = q; t->kind[nb] = BMO_BIT; return;
+    }
     uint16_t* p = gap_clone(g, gap_len(g));
     if (invert) p[0] ^= 1u;                      /* gap_invert */
     t->blk[nb] = p; t->kind[nb] = BMO_GAP;

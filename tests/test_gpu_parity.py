@@ -245,7 +245,9 @@ def test_differential_vs_oracle(ctx, port, dq, cdq, nvec, agg_path):
     for i, j in [(0, 1), (1, 5), (2, nvec - 1)]:
         for op in range(4):
             t = bm.bvector._op2(op, gv[i], gv[j], bm.opt_none)
-            assert (t.to_words(nwb) == port.op2(op, pv[i], pv[j]).to_words(nwb)).all()
+            e = port.op2(op, pv[i], pv[j])
+            assert (t.to_words(nwb) == e.to_words(nwb)).all()
+            assert t.block_table()[0].tolist() == (e.flatten()[0].tolist() + [0] * 64)[:t.info()["nblocks"]], (op, i, j)
             assert bm._count_op2(op, gv[i], gv[j]) == port.count_op2(op, pv[i], pv[j])
     # rank / select against the oracle on a mixed vector
     v, p = gv[1], pv[1]
