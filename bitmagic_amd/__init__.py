@@ -1825,3 +1825,7 @@ class gslice_scanner(slice_scanner):
         if g is None:
             return None, False
         return self.agg.combine_and_sub(g[0], g[1])
+
+
+from ._str_scanner import str_scanner, str_search_groups  # noqa: E402,F401
+__all__ += ["str_scanner", "str_search_groups"]

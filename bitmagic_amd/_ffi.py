@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BMX_LIB") or os.path.join(_HERE, "lib", "libbmx.so")
 
 OK, ERR_BADALLOC, ERR_BADARG, ERR_RANGE, ERR_DEVICE = 0, 1, 2, 3, 4
-RC_BATCH_MAX = 8            # BMX_RC_BATCH_MAX of include/bmx.h: thresholds per launch of bmx_slice_range_counts
+EQK_MAX_PLANES = 1024       # BMX_EQK_MAX_PLANES of include/bmx.h: planes bmx_slice_eq_keys takes
+RC_BATCH_MAX = 8           # BMX_RC_BATCH_MAX of include/bmx.h: thresholds per launch of bmx_slice_range_counts
 
 
 class BmxError(RuntimeError):
@@ -96,6 +97,7 @@ def lib() -> C.CDLL:
         "bmx_slice_compare_signed": (i32, [vp, P(vp), C.c_size_t, i32, C.c_int64, C.c_int64, u64, vp, P(vp), P(u64)]),
         "bmx_slice_compare_stat": (i32, [vp, P(vp), C.c_size_t, i32, u64, u64, u64, vp, P(u64), P(u64)]),
         "bmx_slice_eq_counts": (i32, [vp, P(vp), C.c_size_t, vp, C.c_size_t, u64, vp, vp]),
+        "bmx_slice_eq_keys": (i32, [vp, P(vp), C.c_size_t, u64, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]),
         "bmx_slice_range_counts": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp]),
         "bmx_slice_range_counts_stat": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp, P(u64), P(u32)]),
         "bmx_slice_range_counts_signed": (i32, [vp, P(vp), C.c_size_t, vp, vp, C.c_size_t, u64, vp, vp]),

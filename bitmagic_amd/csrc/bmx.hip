@@ -22,6 +22,7 @@
 #include "bmx_kernels17.h"
 #include "bmx_kernels18.h"
 #include "bmx_kernels19.h"
+#include "bmx_kernels20.h"
 
 #include <algorithm>
 #include <atomic>
@@ -907,6 +908,9 @@ static int ctx_set_tuning(bmx_ctx* ctx, const char* key, int value)
     else if (k == "pair_loop") { ARGCHK(value >= -1 && value <= 5); ctx->pair_loop = value; }
     else if (k == "eq_big_shape") { ARGCHK(value >= 0 && value <= 2); ctx->eq_big_shape = value; }
     else if (k == "eq_big") { ARGCHK(value >= -1 && value <= 1); ctx->eq_big = value; }
+    else if (k == "eqk_fp_bits") { ARGCHK(value >= 0 && value <= 32); ctx->eqk_fp_bits = value; }
+    else if (k == "eqk_pass_keys") { ARGCHK(value >= 0); ctx->eqk_pass_keys = value; }
+    else if (k == "eqk_expand_kb") { ARGCHK(value >= 0 && value <= (32 << 20)); ctx->eqk_expand_kb = value; }
     else if (k == "coll_split") { ARGCHK(value == 0 || value == 1); ctx->coll_split = value; }
     else if (k == "coll_build") { ARGCHK(value >= -1 && value <= 1); ctx->coll_build = value; }
     else if (k == "coll_window") { ARGCHK(value >= 0); ctx->coll_window = value; }
@@ -1065,7 +1069,7 @@ int bmx_ctx_create(int device, void* stream, bmx_ctx** out)
     // an invalid value is ignored (the default stays)
     static const char* const env_keys[][2] = {
         {"BMX_PIPE_UNROLL", "pipe_unroll"}, {"BMX_PIPE_ROWS", "pipe_rows"}, {"BMX_PIPE_NT", "pipe_nt"},
-        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_RC_BATCH", "rc_batch"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}, {"BMX_HITS_TABLE_KB", "hits_table_kb"}};
+        {"BMX_PIPE_WG", "pipe_wg"}, {"BMX_PIPE_WINDOW", "pipe_window"}, {"BMX_PIPE_SPLIT", "pipe_split"}, {"BMX_OR_TILE", "or_tile"}, {"BMX_OR_ROWS", "or_rows"}, {"BMX_OR_DEPTH", "or_depth"}, {"BMX_OR_WINDOW", "or_window"}, {"BMX_DIRECT_COLS", "direct_cols"}, {"BMX_FF_WINDOW", "ff_window"}, {"BMX_RC_BATCH", "rc_batch"}, {"BMX_GAP_COUNT", "gap_count"}, {"BMX_AND_ROWS", "and_rows"}, {"BMX_AGG_SHAPE", "agg_shape"}, {"BMX_AND_ROWS_WG", "and_rows_wg"}, {"BMX_AND_ROWS_DEPTH", "and_rows_depth"}, {"BMX_AND_ROWS_NT", "and_rows_nt"}, {"BMX_AND_ROWS_IPW", "and_rows_ipw"}, {"BMX_RANGE_HALVES", "range_halves"}, {"BMX_PAIR_STREAM", "pair_stream"}, {"BMX_PAIR_WGS", "pair_wgs"}, {"BMX_RS_LANES", "rs_lanes"}, {"BMX_RS_SELECT_TOP", "rs_select_top"}, {"BMX_RS_SELECT_SEL", "rs_select_sel"}, {"BMX_RS_LINES", "rs_lines"}, {"BMX_RS_SELECT_LINES", "rs_select_lines"}, {"BMX_RS_SDIR_SHIFT", "rs_sdir_shift"}, {"BMX_COLL_SHAPE", "coll_shape"}, {"BMX_COLL_WINDOW", "coll_window"}, {"BMX_COLL_SPLIT", "coll_split"}, {"BMX_COLL_BUILD", "coll_build"}, {"BMX_EQ_BIG", "eq_big"}, {"BMX_PAIR_LOOP", "pair_loop"}, {"BMX_PAIR_NT", "pair_nt"}, {"BMX_EQ_BIG_SHAPE", "eq_big_shape"}, {"BMX_OP2_WGS", "op2_wgs"}, {"BMX_OP2_LOOP", "op2_loop"}, {"BMX_OP2_NT", "op2_nt"}, {"BMX_GAP_PACK", "gap_pack"}, {"BMX_COLL_MEMBERS", "coll_members"}, {"BMX_XCD_SWIZZLE", "xcd_swizzle"}, {"BMX_RANKC_PATH", "rankc_path"}, {"BMX_HITS_TABLE_KB", "hits_table_kb"}, {"BMX_EQK_FP_BITS", "eqk_fp_bits"}, {"BMX_EQK_PASS_KEYS", "eqk_pass_keys"}, {"BMX_EQK_EXPAND_KB", "eqk_expand_kb"}};
     for (auto& kv : env_keys)
         if (const char* e = getenv(kv[0])) (void)ctx_set_tuning(ctx.get(), kv[1], atoi(e));
     g_last_error.clear();
@@ -4406,6 +4410,186 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
     bufs.clear();
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q) if (slot[q] >= 0) counts[q] = ucount[(size_t)slot[q]];
+    return BMX_OK;
+ABI_END }
+
+// The all-zero key of bmx_slice_eq_keys (the empty string): rows < size, not NULL where a not-NULL vector is given, with every
+// plane clear -- find_zero with null correction (src/bmsparsevec_algo.h:3412-3415, 2290) -- as one AND-SUB group through the
+// aggregator: AND = [0, size) and not_null, SUB = every plane.
+static int eqk_zero_key(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                        bool want_count, bool want_first, uint64_t* count, int* found, uint64_t* first)
+{
+    *count = 0; *found = 0; *first = 0;
+    if (!size) return BMX_OK;
+    const uint64_t range[2] = {0, size - 1};
+    bmx_vec* r = nullptr;
+    int rc = bmx_vec_from_ranges(ctx, range, 8, 1, size, &r); if (rc) return rc;
+    Owned<bmx_vec> rng(r);
+    std::vector<const bmx_vec*> a{rng.get()}, s;
+    if (not_null) a.push_back(not_null);
+    for (size_t i = 0; i < nslices; ++i) if (slices[i]) s.push_back(slices[i]);
+    if (want_count) {
+        bmx_vec* t = nullptr; int any = 0;
+        if ((rc = bmx_agg_and_sub(ctx, a.data(), a.size(), s.data(), s.size(), &t, &any))) return rc;
+        Owned<bmx_vec> res(t);
+        if (any && (rc = bmx_count(ctx, res.get(), count))) return rc;
+    }
+    if (want_first && (rc = bmx_find_first_and_sub(ctx, a.data(), a.size(), s.data(), s.size(), found, first))) return rc;
+    return BMX_OK;
+}
+
+// counts[q] / first[q] / found[q] of n wide keys in one pass over the planes per table-full of keys (k_slice_eq_keys,
+// bmx_kernels20.h); what n AND-SUB groups of prepare_and_sub_aggregator with prefix_sub compute (src/bmsparsevec_algo.h:2546-2588)
+int bmx_slice_eq_keys(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                      const uint8_t* keys, size_t key_bytes, size_t n, uint64_t* counts, uint64_t* first, uint8_t* found)
+{ ABI_TRY
+    ARGCHK(ctx && (nslices == 0 || slices));
+    ARGCHK(!not_null || not_null->ctx == ctx);
+    ARGCHK(n == 0 || (keys && (counts || first || found)));
+    if (nslices > BMX_EQK_MAX_PLANES) { g_last_error = "more than BMX_EQK_MAX_PLANES planes"; return BMX_ERR_RANGE; }
+    const uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    const uint32_t ncols = (uint32_t)nblocks64;
+    const uint32_t T = (uint32_t)((nslices + 31) / 32);
+    std::vector<uint32_t> present(T, 0u);
+    for (size_t i = 0; i < nslices; ++i) if (slices[i]) {
+        if (slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
+        present[i >> 5] |= 1u << (i & 31);
+    }
+    if (!n) return BMX_OK;
+    int rc = set_dev(ctx); if (rc) return rc;
+    for (size_t q = 0; q < n; ++q) { if (counts) counts[q] = 0; if (first) first[q] = 0; if (found) found[q] = 0; }
+    // distinct non-zero keys that can match at all, as T words each (bit b of octet j = plane 8 j + b); a key with a bit at or
+    // beyond nslices or in an absent plane matches nothing (:2569); the all-zero key goes through the aggregator
+    std::vector<uint32_t> ukeys; std::vector<int64_t> slot(n, -1);
+    size_t nu = 0;
+    {
+        std::unordered_map<std::string, uint32_t> seen;
+        std::vector<uint32_t> w(T);
+        bool zero_done = false; uint64_t zc = 0, zf = 0; int zfound = 0;
+        for (size_t q = 0; q < n; ++q) {
+            const uint8_t* kq = keys + q * key_bytes;
+            std::fill(w.begin(), w.end(), 0u);
+            bool zero = true, impossible = false;
+            for (size_t j = 0; j < key_bytes; ++j) {
+                if (!kq[j]) continue;
+                zero = false;
+                if ((j >> 2) >= T) { impossible = true; break; }
+                w[j >> 2] |= (uint32_t)kq[j] << ((j & 3) * 8);
+            }
+            if (zero) {
+                if (!zero_done) { if ((rc = eqk_zero_key(ctx, slices, nslices, size, not_null, counts != nullptr, first || found, &zc, &zfound, &zf))) return rc; zero_done = true; }
+                if (counts) counts[q] = zc;
+                if (first) first[q] = zf;
+                if (found) found[q] = (uint8_t)(zfound != 0);
+                continue;
+            }
+            for (uint32_t t = 0; t < T && !impossible; ++t) if (w[t] & ~present[t]) impossible = true;
+            if (impossible) continue;
+            std::string key(reinterpret_cast<const char*>(w.data()), (size_t)T * 4);
+            auto it = seen.find(key);
+            if (it == seen.end()) { it = seen.emplace(std::move(key), (uint32_t)nu).first; ukeys.insert(ukeys.end(), w.begin(), w.end()); ++nu; }
+            slot[q] = it->second;
+        }
+    }
+    if (!nu || !ncols) return BMX_OK;
+    // workgroup shape and keys per pass: what the LDS left by the per-wave arrays holds at 16 B per slot
+    uint32_t nw = 8, cap = 0;
+    for (; nw >= 1; nw >>= 1) {
+        const size_t fixed = eqk_lds_bytes(0, T, nw);
+        if (fixed + 64u * 16u <= ctx->max_lds_bytes) {
+            const uint32_t slots = (uint32_t)(((ctx->max_lds_bytes - fixed) / 16u) & ~(size_t)63u);
+            if (slots >= 128u) { cap = (slots - 64u) * 2u / 3u; if (cap >= 64u || nw == 1) break; }
+        }
+    }
+    if (!cap) { g_last_error = "not enough LDS for the key table"; return BMX_ERR_RANGE; }
+    while (cap && EQK_SLOTS(cap) * 16u + eqk_lds_bytes(0, T, nw) > ctx->max_lds_bytes) --cap;
+    if (ctx->eqk_pass_keys > 0) cap = std::min<uint32_t>(cap, (uint32_t)ctx->eqk_pass_keys);
+    if (!cap) { g_last_error = "not enough LDS for the key table"; return BMX_ERR_RANGE; }
+    const uint32_t fp_mask = (ctx->eqk_fp_bits <= 0 || ctx->eqk_fp_bits >= 32) ? ~0u : (1u << ctx->eqk_fp_bits) - 1u;
+    // every pass's table: [fingerprints: tab][keys: tab x T]; slot numbers run on across the passes
+    struct Pass { size_t u0; uint32_t nv, tab; size_t blob_off, slot0; };
+    std::vector<Pass> passes;
+    const size_t npass = (nu + cap - 1) / cap, chunk = (nu + npass - 1) / npass;
+    size_t blob_words = 0, nslots = 0;
+    for (size_t u0 = 0; u0 < nu; u0 += chunk) {
+        const uint32_t nv = (uint32_t)std::min(chunk, nu - u0), tab = EQK_SLOTS(nv);
+        passes.push_back({u0, nv, tab, blob_words, nslots});
+        blob_words += (size_t)tab * (1u + T); nslots += tab;
+    }
+    std::vector<uint32_t> blob(blob_words, 0u);
+    std::vector<size_t> where(nu);
+    for (const Pass& p : passes) {
+        uint32_t* fpv = blob.data() + p.blob_off; uint32_t* kw = fpv + p.tab;
+        std::fill(fpv, fpv + p.tab, (uint32_t)EQK_EMPTY);
+        for (uint32_t k = 0; k < p.nv; ++k) {
+            const uint32_t* w = ukeys.data() + (p.u0 + k) * T;
+            uint32_t hsh = 0;
+            for (uint32_t t = 0; t < T; ++t) hsh = eqk_fold(hsh, w[t]);
+            const uint32_t fp = eqk_finish(hsh, fp_mask);
+            uint32_t h = eqk_home(fp, p.tab);
+            while (fpv[h] != EQK_EMPTY) h = h + 1u == p.tab ? 0u : h + 1u;
+            fpv[h] = fp; memcpy(kw + (size_t)h * T, w, (size_t)T * 4);
+            where[p.u0 + k] = p.slot0 + h;
+        }
+    }
+    // GAP-holding planes are expanded to raw bits a window of block columns at a time ("eqk_expand_kb"): counts add and firsts
+    // take the minimum across windows (the per-slot arrays stay on the device until the last window)
+    std::vector<size_t> gap_planes;
+    for (size_t i = 0; i < nslices; ++i) if (slices[i] && slices[i]->counts[BMX_GAP]) gap_planes.push_back(i);
+    uint32_t wcols = ncols;
+    if (!gap_planes.empty()) {
+        const uint64_t per_col = (uint64_t)gap_planes.size() * 8192u;
+        wcols = (uint32_t)std::min<uint64_t>(ncols, std::max<uint64_t>(1, (uint64_t)ctx->eqk_expand_kb * 1024u / per_col));
+    }
+    DevBuf d_raw(ctx), d_planes(ctx), d_blob(ctx), d_res(ctx);
+    if (!gap_planes.empty() && (rc = dmalloc(ctx, &d_raw.p, (size_t)gap_planes.size() * wcols * 8192u))) return rc;
+    std::vector<EqkPlane> hpl(nslices);
+    memset(hpl.data(), 0, hpl.size() * sizeof(EqkPlane));
+    for (size_t i = 0; i < nslices; ++i) if (slices[i]) { hpl[i].desc = slices[i]->d_desc; hpl[i].nblk = slices[i]->nblocks; }
+    for (size_t g = 0; g < gap_planes.size(); ++g) hpl[gap_planes[g]].raw = (const uint4*)d_raw + g * (size_t)wcols * 512u;
+    if ((rc = dmalloc(ctx, &d_planes.p, hpl.size() * sizeof(EqkPlane))) || (rc = dmalloc(ctx, &d_blob.p, blob_words * 4)) ||
+        (rc = dmalloc(ctx, &d_res.p, nslots * 16))) return rc;
+    u64* d_cnt = (u64*)d_res; u64* d_first = d_cnt + nslots;
+    std::vector<uint64_t> res(nslots * 2);
+    rc = h2d_staged(ctx, d_planes.p, hpl.data(), hpl.size() * sizeof(EqkPlane));
+    if (!rc) rc = h2d_staged(ctx, d_blob.p, blob.data(), blob_words * 4);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(d_cnt, 0, nslots * 8, ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemsetAsync(d_first, 0xFF, nslots * 8, ctx->stream);
+    size_t lds_max = 0;
+    for (const Pass& p : passes) lds_max = std::max(lds_max, eqk_lds_bytes(p.tab, T, nw));
+    if (!rc && e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_slice_eq_keys), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+    for (uint32_t c0 = 0; c0 < ncols && !rc && e == hipSuccess; c0 += wcols) {
+        const uint32_t c1 = std::min(ncols, c0 + wcols), wn = c1 - c0;
+        for (size_t g = 0; g < gap_planes.size() && e == hipSuccess; ++g) {
+            const bmx_vec* sv = slices[gap_planes[g]];
+            const uint32_t rem = sv->nblocks > c0 ? sv->nblocks - c0 : 0u;
+            hipLaunchKernelGGL(k_vec_expand, dim3((wn + 3) / 4), dim3(256), 0, ctx->stream, rem ? sv->d_desc + c0 : sv->d_desc, rem, wn,
+                               (uint4*)d_raw + g * (size_t)wcols * 512u);
+            e = hipGetLastError();
+        }
+        for (size_t i = 0; i < passes.size() && e == hipSuccess; ++i) {
+            const Pass& p = passes[i];
+            const u32* d_fp = (const u32*)d_blob + p.blob_off;
+            const u32 grid = std::min<u32>((wn * EQK_PARTS + nw - 1u) / nw, 256u);
+            hipLaunchKernelGGL(k_slice_eq_keys, dim3(grid), dim3(nw * 64u), eqk_lds_bytes(p.tab, T, nw), ctx->stream,
+                               (const EqkPlane*)d_planes, (u32)nslices, T, c0, c1, size, d_fp, d_fp + p.tab, p.tab, fp_mask,
+                               d_cnt + p.slot0, d_first + p.slot0);
+            e = hipGetLastError();
+        }
+    }
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(res.data(), d_cnt, nslots * 16, hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (!rc && (e != hipSuccess || e2 != hipSuccess)) rc = fail_hip(e != hipSuccess ? e : e2, "bmx_slice_eq_keys", __LINE__);
+    if (rc) return rc;
+    for (size_t q = 0; q < n; ++q) if (slot[q] >= 0) {
+        const size_t s = where[(size_t)slot[q]];
+        const bool hit = res[s] != 0;
+        if (counts) counts[q] = res[s];
+        if (first) first[q] = hit ? res[nslots + s] : 0;
+        if (found) found[q] = (uint8_t)hit;
+    }
     return BMX_OK;
 ABI_END }
 

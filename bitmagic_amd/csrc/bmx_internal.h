@@ -117,6 +117,9 @@ struct bmx_ctx {
     int op2_wgs = 4;           // workgroups per CU of the streaming materialised pairwise kernel (k_op2_stream)
     int eq_big_shape = 2;      // lean table: 2 = 768 threads at 3 waves per SIMD, 8 filter reads in flight, 256 Kbit filter, 512-entry queues -- taken for every batch size over more than 16 planes; 1 = 512 threads, 2 waves per SIMD; 0 = 128 Kbit filter + 1,024-entry queues
     int eq_big = -1;           // batched equality counts: -1 = lean 9,216-value table when the batch has more than 2,048 values, 0 = never, 1 = always
+    int eqk_fp_bits = 0;       // bmx_slice_eq_keys: fingerprint bits kept (0 = all 32; fewer: the exact verification decides more rows -- a test hook, results never depend on it)
+    int eqk_pass_keys = 0;     // ... keys per pass over the planes (0 = what the LDS table holds)
+    int eqk_expand_kb = 256 * 1024;   // ... KiB of raw bits the GAP-holding planes may be expanded into at a time (a window of block columns; 0 = one column per window)
     int coll_window = 0;       // block columns per launch of k_coll_apply (0 = one launch)
     int rs_lines = 1;          // build_rs_index also lays the vector out as rank lines (one 128-B line per rank query; +108 % of the raw bits): 1 = where that is <= 2 x the vector's own device bytes (bit-blocks in more than about half of its block columns), 2 = always, 0 = never
     int rs_sdir_shift = 0;     // ones per select-directory entry = 2^this; 0 = from the density (an entry per ~10 lines); grown when the directory would pass 8 MB

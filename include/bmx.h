@@ -317,6 +317,33 @@ int bmx_slice_compare_stat(bmx_ctx* ctx, const bmx_vec* const* slices, size_t ns
 int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* values, size_t n,
                         uint64_t size, const bmx_vec* not_null, uint64_t* counts);
 
+/* ---- string search: the find_eq_str half of bm::sparse_vector_scanner over bm::str_sparse_vector<> ----
+ * (src/bmsparsevec_algo.h:1194-1235, 3263-3436; the AND-SUB group of one string: prepare_and_sub_aggregator, :2546-2588).
+ * A batch of equality searches with WIDE keys in one pass over any number of planes (k_slice_eq_keys, bmx_kernels20.h: the
+ * bit-matrix transposition of bmx_slice_eq_counts tile by tile, a fingerprint per row, an LDS table lookup, and an exact
+ * comparison of every candidate row with the key): a dictionary lookup or a dictionary join over a string column, where the
+ * reference runs one group per string (find_eq_str(pipe), :3263).
+ * counts[q] = rows equal to key q, first[q] / found[q] = the lowest such row (first[q] = 0 where found[q] = 0).
+ * key q = keys[q * key_bytes .. + key_bytes): bit b of octet j is plane 8 * j + b (str_sparse_vector's numbering,
+ * src/bmstrsparsevec.h:1423); the caller pads with zeros (and applies the container's remap table first, if it has one).
+ * Row i < size matches iff for every p < max(nslices, 8 * key_bytes) the plane bit equals the key bit, absent or missing bits on
+ * either side reading as 0 (slices[p] == NULL, a plane shorter than the column, a key shorter than the column): a key with a
+ * bit no plane holds matches nothing (the pre-screen of :2569); a key shorter than the column matches only rows whose further
+ * octets are clear (prefix_sub, :2575-2586: "ab" does not match "abc").  The all-zero key (the empty string) matches the rows
+ * < size with every plane clear that are not NULL where not_null is given (find_zero with null correction, :3412-3415, 2290;
+ * computed as an AND-SUB group through the aggregator); not_null is consulted for nothing else, as in the reference.
+ * Duplicate keys each get the answer.  n == 0: BMX_OK, nothing is written.  size == 0 and nslices == 0 are ordinary inputs.
+ * The entry always runs the batch kernel for non-zero keys (bmx::str_scanner chooses between it and the pipeline).
+ * BMX_ERR_BADARG: null context, a vector of another context, keys NULL or all three outputs NULL with n > 0.
+ * BMX_ERR_RANGE: nslices > BMX_EQK_MAX_PLANES, or a column of more than 2^20 blocks.
+ * Planes that hold GAP blocks are expanded to raw bits a window of block columns at a time (never whole).
+ * Tuning keys (results never depend on them): "eqk_fp_bits" 0|1..32 (fingerprint bits kept; 0 = all), "eqk_pass_keys" 0|N (keys
+ * per pass over the planes; 0 = what the LDS table holds), "eqk_expand_kb" 0..33554432 (KiB of expanded GAP planes per window). */
+#define BMX_EQK_MAX_PLANES 1024
+int bmx_slice_eq_keys(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
+                      const uint8_t* keys, size_t key_bytes, size_t n,
+                      uint64_t* counts /* or NULL */, uint64_t* first /* or NULL */, uint8_t* found /* or NULL */);
+
 /* a batch of range searches, counts only -- what a loop of sparse_vector_scanner::find_range / find_gt / find_le + count() computes
  * (src/bmsparsevec_algo.h:1135-1174, 2690-2900; signed containers: find_gt_horizontal_s :1484, 3033-3160): a histogram over bin
  * edges, quantile boundaries, COUNT(*) .. WHERE x BETWEEN a AND b for a list of intervals, the ranks of a list of values.  The

@@ -19,6 +19,7 @@
 #include "bvector.hpp"
 #include "group.hpp"
 #include "sv_algo.hpp"
+#include "str_scanner.hpp"
 
 namespace bmx {
 
@@ -584,6 +585,52 @@ void set2set_11_remap(context& ctx, const typename SV::bvector_type& bv_in, cons
     set2set_11_transform t;
     t.remap(d_in, col, d_out);
     download(d_out, bv_out);
+}
+
+/// a host bm::str_sparse_vector<char, bm::bvector<>, N> bound into a bmx::str_scanner (bmx/str_scanner.hpp): its planes
+/// (get_slice(i) up to get_bmatrix().rows_not_null()), its NULL vector, and -- for a remapped vector -- its code tables.
+/// get_remap_matrix() (src/bmstrsparsevec.h:1583) is the decoding matrix (row = octet position, column = code, value =
+/// character); the scanner wants the encoding one, which the reference derives the same way (recalc_remap_matrix2).
+/// `store` owns the device vectors and must outlive the scanner's use of them.
+/// (get_remap_matrix() is a protected member the reference opens to its own scanner: a derived class may name it)
+template <class STR_SV>
+struct str_sv_remap_access : STR_SV {
+    typedef const typename STR_SV::remap_matrix_type* (STR_SV::*getter)() const;
+    static getter get() { return static_cast<getter>(&str_sv_remap_access::get_remap_matrix); }
+};
+template <class STR_SV>
+void bind_str_scanner(context& ctx, const STR_SV& sv, str_scanner& sc, std::vector<bvector>& store)
+{
+    const unsigned planes = (unsigned)sv.get_bmatrix().rows_not_null();
+    const uint32_t nblocks = (uint32_t)(((uint64_t)sv.size() + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS);
+    store.clear(); store.reserve(planes + 1u);
+    std::vector<int> slot(planes, -1);
+    for (unsigned i = 0; i < planes; ++i) {
+        if (const typename STR_SV::bvector_type* bv = sv.get_slice(i)) {
+            store.emplace_back(ctx);
+            upload(*bv, store.back(), nblocks ? nblocks : 1);
+            slot[i] = (int)store.size() - 1;
+        }
+    }
+    int null_slot = -1;
+    if (const typename STR_SV::bvector_type* bn = sv.get_null_bvector()) {
+        store.emplace_back(ctx);
+        upload(*bn, store.back(), nblocks ? nblocks : 1);
+        null_slot = (int)store.size() - 1;
+    }
+    std::vector<const bvector*> pl(planes, nullptr);
+    for (unsigned i = 0; i < planes; ++i) if (slot[i] >= 0) pl[i] = &store[(size_t)slot[i]];
+    sc.bind(pl, sv.size(), null_slot >= 0 ? &store[(size_t)null_slot] : nullptr);
+    if (sv.is_remap()) {
+        const typename STR_SV::remap_matrix_type* m = (sv.*str_sv_remap_access<STR_SV>::get())();
+        const size_t octets = m->rows(), codes = m->cols() < 256 ? m->cols() : 256;
+        std::vector<uint8_t> tables(octets * 256u, 0);
+        for (size_t i = 0; i < octets; ++i) {
+            const unsigned char* row = m->row((typename STR_SV::remap_matrix_type::size_type)i);
+            for (size_t c = 1; c < codes; ++c) if (row[c]) tables[i * 256u + row[c]] = (uint8_t)c;
+        }
+        sc.set_remap(tables.data(), octets);
+    } else sc.set_remap(nullptr, 0);
 }
 
 } // namespace bmx
