@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -3775,6 +3776,22 @@ static int ff_windows(const bmx_ctx* ctx, u32 col_from, u32 col_to, u32 first, L
         c = e; w *= 4u;
     }
     return BMX_OK;
+}
+// One first-hit search: arm the best-index word (d_small[0] = ~0), enqueue every window of ff_windows through the caller's
+// launch, copy the word back, synchronise once -- also after a failed launch: the windows before it are in flight over the
+// caller's tables -- and decode: *found / *idx are set on a hit and left as the caller cleared them otherwise.
+template <class Launch>
+static int first_hit_run(bmx_ctx* ctx, const char* what, u32 col_from, u32 col_to, u32 first, Launch&& launch, int* found, uint64_t* idx)
+{
+    int rc = BMX_OK;
+    hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
+    if (e == hipSuccess) rc = ff_windows(ctx, col_from, col_to, first, launch);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, what, __LINE__);
+    if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
+    return BMX_OK;
 } }
 
 static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and, const bmx_vec* const* src_sub, size_t n_sub,
@@ -3804,43 +3821,25 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     const u32 ncv = col_to > col_from ? col_to - col_from : 0u;
     // long lists: any number of columns (windows); short lists: the size rule of use_direct
     const bool direct = use_direct(ctx, (n_and + n_sub < 24u) ? ncv : (ncv ? 1u : 0u), n_and + n_sub) != 0;
-    auto windows = [&](u32 first, auto&& launch) -> int { return ff_windows(ctx, col_from, col_to, first, launch); };
     if (direct) {
         // many operands: a workgroup of 8 waves per column straight from the descriptor tables (k_direct); 64 columns first
         // (a hit in the first blocks is answered after ~1/8 of what two workgroups per CU would read)
         OperandTable ops; DevBuf d_tab(ctx);
         if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = direct_table(ctx, &ops, d_tab))) return rc;
-        hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
-        if (e == hipSuccess)
-            rc = windows(n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) { return direct_launch(DIRECT_FIND_FIRST, ctx, ops, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt); });
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        d_tab.reset();
-        if (rc) return rc;
-        if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, "bmx_find_first_and_sub", __LINE__);
-        if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
-        return BMX_OK;
+        return first_hit_run(ctx, "bmx_find_first_and_sub", col_from, col_to, n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) {
+            return direct_launch(DIRECT_FIND_FIRST, ctx, ops, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt);
+        }, found, idx);
     }
     bmx_pipeline* praw = nullptr;
     if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw))) return rc;
     Owned<bmx_pipeline> p(praw);
-    hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
-    if (e == hipSuccess) {
-        size_t lds = p->has_gap ? 4 * 2048 * 4 : 0;
-        rc = windows(512u, [&](u32 c0, u32 c1) {                             // a wave per column: first window = 2 waves per CU
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_find_first_and_sub<2>), dim3((c1 - c0 + 3) / 4), dim3(256), lds, ctx->stream,
-                               p->d_dmat, p->d_meta + 1, p->d_meta + 2, p->col_stride, c0, c1, has_mask, mf, mt, ctx->d_small);
-            hipError_t le = hipGetLastError();
-            return le == hipSuccess ? BMX_OK : fail_hip(le, "k_find_first_and_sub", __LINE__);
-        });
-    }
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
-    hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    p.reset();
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, "bmx_find_first_and_sub", __LINE__);
-    if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
-    return BMX_OK;
+    const size_t lds = p->has_gap ? 4 * 2048 * 4 : 0;
+    return first_hit_run(ctx, "bmx_find_first_and_sub", col_from, col_to, 512u, [&](u32 c0, u32 c1) {   // a wave per column: first window = 2 waves per CU
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_find_first_and_sub<2>), dim3((c1 - c0 + 3) / 4), dim3(256), lds, ctx->stream,
+                           p->d_dmat, p->d_meta + 1, p->d_meta + 2, p->col_stride, c0, c1, has_mask, mf, mt, ctx->d_small);
+        const hipError_t le = hipGetLastError();
+        return le == hipSuccess ? BMX_OK : fail_hip(le, "k_find_first_and_sub", __LINE__);
+    }, found, idx);
 }
 
 int bmx_agg_and_sub_indices(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
@@ -3869,6 +3868,28 @@ int bmx_find_first_and_sub_range(bmx_ctx* ctx, const bmx_vec* const* src_and, si
     return find_first_impl(ctx, src_and, n_and, src_sub, n_sub, true, from, to, found, idx);
 ABI_END }
 
+// The tail of a call whose kernel either stored into the vector of result_begin (v) or added into the count slots (no v): the
+// slot sum and its copy, or result_finish; the call's one synchronise; then the operand table goes (before a count pass
+// allocates) and the vector is handed over -- with its count where the caller wants both -- or *count = the slot sum.
+// What else the caller had copied into h_small before the tail is there to read when it returns.
+// The rule for every exit of the scanner entries below: a call that has enqueued a copy into host memory it owns (a vector on
+// its stack, not the context's h_small) waits for the stream on every path out, failed launches included; device buffers need
+// no wait of their own -- they are pooled, and the pool's next user is enqueued behind whatever still reads them.
+static int vec_or_count_tail(bmx_ctx* ctx, Owned<bmx_vec>& v, BlockStat* st, u32* offs, DevBuf& d_tab, bmx_vec** result, uint64_t* count)
+{
+    int rc;
+    if (!v) {
+        hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
+        KCHK();
+        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
+    } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    d_tab.reset();
+    if (!v) { *count = ctx->h_small[0]; return BMX_OK; }
+    *result = v.release();
+    return count ? bmx_count(ctx, *result, count) : BMX_OK;
+}
+
 // aggregator::combine_shift_right_and  src/bmaggregator.h:552,2494 (count form: set_compute_count, :363,2595)
 static int shift_right_and_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int opt_compress, int any,
                                 bmx_vec** result, int* found, uint64_t* count)
@@ -3895,19 +3916,8 @@ static int shift_right_and_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t 
         hipLaunchKernelGGL(k_keep_first_block, dim3(1), dim3(1024), 0, ctx->stream, st, v->d_desc, ncols);
         KCHK();
     }
-    if (!result) {
-        hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (result) {
-        if (found) *found = vec_any_block(v.get());
-        *result = v.release();
-    } else {
-        *count = ctx->h_small[0];
-        if (found) *found = *count != 0;
-    }
+    if ((rc = vec_or_count_tail(ctx, v, st, offs, d_tab, result, count))) return rc;
+    if (found) *found = result ? vec_any_block(*result) : *count != 0;
     return BMX_OK;
 }
 
@@ -3924,73 +3934,87 @@ int bmx_agg_shift_right_and_count(bmx_ctx* ctx, const bmx_vec* const* src, size_
     return shift_right_and_impl(ctx, src, n, 0, 0, nullptr, nullptr, count);
 ABI_END }
 
+// ---- bit-sliced columns: one description and one check (the scanner entries below) ----
+// A column as its entry received it, checked: the magnitude planes (a null entry = a plane that does not exist), the sign
+// plane of a signed container (slices[0] there; s2u encoding, src/bmbmatrix.h:2536-2548), the not-NULL vector, the rows and
+// the block columns they span.
+struct SliceColumn {
+    const bmx_vec* const* mag = nullptr; size_t nmag = 0;
+    const bmx_vec* sign = nullptr; const bmx_vec* not_null = nullptr;
+    uint64_t size = 0; uint32_t ncols = 0;
+};
+// max_planes: magnitude planes the entry takes (a signed column may pass one more: its sign plane); nn_text: what a not-NULL
+// vector of another context is refused with -- the entries that list it in their operand table (mismatch, values, remap) have
+// always reported it as a slice
+static const char* const NN_OTHER_CTX = "bad argument: !not_null || not_null->ctx == ctx";
+static const char* const SLICE_OTHER_CTX = "slice belongs to another context";
+static int slice_column(const bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, size_t max_planes, bool sgn,
+                        uint64_t size, const bmx_vec* not_null, SliceColumn* c, const char* nn_text = NN_OTHER_CTX)
+{
+    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= max_planes + (sgn ? 1u : 0u));
+    if (not_null && not_null->ctx != ctx) { g_last_error = nn_text; return BMX_ERR_BADARG; }
+    for (size_t i = 0; i < nslices; ++i)
+        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = SLICE_OTHER_CTX; return BMX_ERR_BADARG; }
+    const uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
+    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
+    const size_t skip = sgn && nslices ? 1 : 0;
+    c->mag = slices + skip; c->nmag = nslices - skip;
+    c->sign = skip ? slices[0] : nullptr; c->not_null = not_null;
+    c->size = size; c->ncols = (uint32_t)nblocks64;
+    return BMX_OK;
+}
+
 // sparse_vector_scanner<SV>::find_gt/ge/lt/le/range/eq/zero/nonzero over resident slices (bmx_kernels4.h)
-// shared body of bmx_slice_compare / bmx_slice_compare_signed: `slices` are the planes the magnitude walk runs over;
-// sign / sign_mode: the sign plane of a signed container and how the magnitude predicate combines with it (bmx_kernels4.h);
+typedef decltype(&k_slice_compare<false>) slice_compare_fn;
+static slice_compare_fn slice_compare_kernel(bool halves, bool two, bool sgn)
+{
+    // halves: partial-block passes (fewer accumulators, more waves)
+    // (measured: one bound -- half blocks 0.372 ms, quarter blocks 0.422; two bounds -- half blocks 0.536 ms, quarter blocks 0.473)
+    if (halves) return sgn ? (two ? k_slice_compare_halves<true, 2, true> : k_slice_compare_halves<false, 4, true>)
+                           : (two ? k_slice_compare_halves<true, 2> : k_slice_compare_halves<false, 4>);
+    return sgn ? (two ? k_slice_compare<true, true> : k_slice_compare<false, true>) : (two ? k_slice_compare<true> : k_slice_compare<false>);
+}
+// shared body of bmx_slice_compare / bmx_slice_compare_signed: the magnitude walk runs over col.mag;
+// sign_mode: how the magnitude predicate combines with col.sign (bmx_kernels4.h);
 // null_correct: the predicate admits value 0, so NULL rows (stored as 0) must be removed
-static int slice_compare_impl(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int pred, uint64_t v0, uint64_t v1,
-                              uint64_t size, const bmx_vec* not_null, int null_correct, const bmx_vec* sign, int sign_mode,
+static int slice_compare_impl(bmx_ctx* ctx, const SliceColumn& col, int pred, uint64_t v0, uint64_t v1, int null_correct, int sign_mode,
                               bmx_vec** result, uint64_t* count, uint64_t* plane_bytes)
 {
-    if (result) *result = nullptr;
-    if (count) *count = 0;
-    if (plane_bytes) *plane_bytes = 0;
     int rc = set_dev(ctx); if (rc) return rc;
-    uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    uint32_t ncols = (uint32_t)nblocks64;
+    const uint32_t ncols = col.ncols;
+    const bmx_vec* not_null = col.not_null; const bmx_vec* sign = col.sign;
     OperandTable ops;
-    if ((rc = operand_list(ctx, slices, nslices, nullptr, 0, true, &ops))) return rc;
+    if ((rc = operand_list(ctx, col.mag, col.nmag, nullptr, 0, true, &ops))) return rc;
     const bool sgn = sign_mode != SIGN_NONE || pred == CMP_SRANGE;
     const bool two = pred == BMX_CMP_RANGE || pred == CMP_SRANGE;
     Owned<bmx_vec> v; BlockStat* st = nullptr; u32* offs = nullptr;
-    if (result && (rc = result_begin(ctx, size, ncols, &v, &st, &offs))) return rc;
+    if (result && (rc = result_begin(ctx, col.size, ncols, &v, &st, &offs))) return rc;
     if (!ncols) { if (result) *result = v.release(); return BMX_OK; }
     DevBuf d_tab(ctx);
     if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
     u64* d_stat = plane_bytes ? ctx->d_small + 8 : nullptr;
     if (d_stat) HIPCHK(hipMemsetAsync(d_stat, 0, 8, ctx->stream));
-#define CMP_ARGS dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, \
-        ops.d_descs, ops.d_nblk, (u32)nslices, ncols, pred, v0, v1, size, \
-        not_null ? (const u64*)not_null->d_desc : nullptr, not_null ? not_null->nblocks : 0u, null_correct, \
-        result ? 0 : 1, ctx->xcd_swz, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots, \
-        sign ? (const u64*)sign->d_desc : nullptr, sign ? sign->nblocks : 0u, sign_mode, d_stat
-    if (ctx->range_halves) {                                            // partial-block passes (fewer accumulators, more waves)
-        // (measured: one bound -- half blocks 0.372 ms, quarter blocks 0.422; two bounds -- half blocks 0.536 ms, quarter blocks 0.473)
-        if (sgn) { if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<true, 2, true>), CMP_ARGS);
-                   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<false, 4, true>), CMP_ARGS); }
-        else if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<true, 2>), CMP_ARGS);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare_halves<false, 4>), CMP_ARGS);
-    } else {
-        if (sgn) { if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<true, true>), CMP_ARGS);
-                   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<false, true>), CMP_ARGS); }
-        else if (two) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<true>), CMP_ARGS);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_slice_compare<false>), CMP_ARGS);
-    }
-#undef CMP_ARGS
+    hipLaunchKernelGGL(slice_compare_kernel(ctx->range_halves != 0, two, sgn), dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream,
+                       ops.d_descs, ops.d_nblk, (u32)col.nmag, ncols, pred, v0, v1, col.size,
+                       not_null ? (const u64*)not_null->d_desc : nullptr, not_null ? not_null->nblocks : 0u, null_correct,
+                       result ? 0 : 1, ctx->xcd_swz, v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots,
+                       sign ? (const u64*)sign->d_desc : nullptr, sign ? sign->nblocks : 0u, sign_mode, d_stat);
     KCHK();
-    if (!result) {
-        hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
     if (d_stat) HIPCHK(hipMemcpyAsync(ctx->h_small + 8, d_stat, 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (result && (rc = result_finish(ctx, v.get(), st, offs))) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    d_tab.reset();                                          // (before the count pass below allocates)
-    if (plane_bytes) *plane_bytes = ctx->h_small[8];
-    if (result) {
-        *result = v.release();
-        if (count) { rc = bmx_count(ctx, *result, count); if (rc) return rc; }
-    } else *count = ctx->h_small[0];
-    return BMX_OK;
+    rc = vec_or_count_tail(ctx, v, st, offs, d_tab, result, count);
+    if (!rc && plane_bytes) *plane_bytes = ctx->h_small[8];
+    return rc;
 }
 
 static int slice_compare_unsigned(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int pred, uint64_t v0, uint64_t v1,
                                   uint64_t size, const bmx_vec* not_null, bmx_vec** result, uint64_t* count, uint64_t* plane_bytes)
 {
-    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && pred >= BMX_CMP_GT && pred <= BMX_CMP_NONZERO && (result || count));
-    ARGCHK(!not_null || not_null->ctx == ctx);
+    if (result) *result = nullptr;                                       // (before the column's check: whatever it refuses, nothing stale stays)
+    if (count) *count = 0;
+    if (plane_bytes) *plane_bytes = 0;
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, 64, false, size, not_null, &col); if (rc) return rc;
+    ARGCHK(pred >= BMX_CMP_GT && pred <= BMX_CMP_NONZERO && (result || count));
     if (pred == BMX_CMP_RANGE && v1 < v0) std::swap(v0, v1);              // bm::xor_swap(from, to), :2872
     if (pred == BMX_CMP_ZERO || pred == BMX_CMP_NONZERO) v0 = 0;
     // which results can contain value 0 = where NULL elements hide (needs_null_correct_*, :1703-1735, unsigned)
@@ -4002,7 +4026,7 @@ static int slice_compare_unsigned(bmx_ctx* ctx, const bmx_vec* const* slices, si
     case BMX_CMP_EQ: null_correct = v0 == 0; break;
     default: break;
     }
-    return slice_compare_impl(ctx, slices, nslices, pred, v0, v1, size, not_null, null_correct, nullptr, SIGN_NONE, result, count, plane_bytes);
+    return slice_compare_impl(ctx, col, pred, v0, v1, null_correct, SIGN_NONE, result, count, plane_bytes);
 }
 
 int bmx_slice_compare(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int pred, uint64_t v0, uint64_t v1,
@@ -4022,12 +4046,11 @@ ABI_END }
 int bmx_slice_compare_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int pred, int64_t v0, int64_t v1,
                              uint64_t size, const bmx_vec* not_null, bmx_vec** result, uint64_t* count)
 { ABI_TRY
-    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 65 && pred >= BMX_CMP_GT && pred <= BMX_CMP_NONZERO && (result || count));
-    ARGCHK(!not_null || not_null->ctx == ctx);
-    const bmx_vec* sign = nslices ? slices[0] : nullptr;
-    if (sign && sign->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-    const bmx_vec* const* mag = nslices ? slices + 1 : slices;
-    const size_t nmag = nslices ? nslices - 1 : 0;
+    if (result) *result = nullptr;
+    if (count) *count = 0;
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, 64, true, size, not_null, &col); if (rc) return rc;
+    ARGCHK(pred >= BMX_CMP_GT && pred <= BMX_CMP_NONZERO && (result || count));
     if (pred == BMX_CMP_RANGE && v1 < v0) std::swap(v0, v1);
     // magnitude of a bound: v >= 0 -> v, v < 0 -> -(v + 1)
     auto magn = [](int64_t v) -> uint64_t { return v >= 0 ? (uint64_t)v : (uint64_t)(-(v + 1)); };
@@ -4058,7 +4081,7 @@ int bmx_slice_compare_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t 
     case BMX_CMP_ZERO: kp = CMP_ZERO; mode = SIGN_NONNEG_ONLY; break;                              // sign 0, magnitude 0
     default: kp = CMP_NONZERO; mode = SIGN_NEG_ALL; break;                                          // any magnitude bit, or negative (-1 = sign only)
     }
-    return slice_compare_impl(ctx, mag, nmag, kp, b0, b1, size, not_null, admits0 ? 1 : 0, sign, mode, result, count, nullptr);
+    return slice_compare_impl(ctx, col, kp, b0, b1, admits0 ? 1 : 0, mode, result, count, nullptr);
 ABI_END }
 
 // sparse_vector_find_mismatch / sparse_vector_find_first_mismatch over two resident columns (bmx_kernels17.h): shared body of
@@ -4068,18 +4091,22 @@ static int slice_mismatch_impl(bmx_ctx* ctx, const bmx_vec* const* a, size_t na,
                                const bmx_vec* const* b, size_t nb, uint64_t size_b, const bmx_vec* nn_b, int null_proc,
                                bool first, bmx_vec** result, uint64_t* count, int* found, uint64_t* idx)
 {
-    ARGCHK(ctx && (na == 0 || a) && (nb == 0 || b) && na <= 65 && nb <= 65);
-    ARGCHK(first ? (found && idx) : (result || count));
-    if (result) *result = nullptr;
+    if (result) *result = nullptr;                          // (before the columns' check, as for the comparison entries)
     if (count) *count = 0;
-    if (first) { *found = 0; *idx = 0; }
+    if (found) *found = 0;
+    if (idx) *idx = 0;
+    SliceColumn ca, cb;                                     // (planes as passed: a sign plane is one more row of the XOR)
+    int rc;
+    if ((rc = slice_column(ctx, a, na, 65, false, size_a, nn_a, &ca, SLICE_OTHER_CTX)) ||
+        (rc = slice_column(ctx, b, nb, 65, false, size_b, nn_b, &cb, SLICE_OTHER_CTX))) return rc;
+    ARGCHK(first ? (found && idx) : (result || count));
     if (null_proc != BMX_USE_NULL && null_proc != BMX_NO_NULL) { g_last_error = "null_proc is neither BMX_USE_NULL nor BMX_NO_NULL"; return BMX_ERR_BADARG; }
     if (!first && null_proc == BMX_USE_NULL && !nn_a && !nn_b) {
         // (:760-788: the reference inverts an empty vector of the whole address range there -- every position up to id_max)
         g_last_error = "BMX_USE_NULL without a not-NULL vector on either side: the reference sets every position up to id_max, which no device vector holds";
         return BMX_ERR_BADARG;
     }
-    int rc = set_dev(ctx); if (rc) return rc;
+    if ((rc = set_dev(ctx))) return rc;
     const size_t P = std::max(na, nb);
     std::vector<const bmx_vec*> list(2 * P + 2, nullptr);
     for (size_t i = 0; i < na; ++i) list[i] = a[i];
@@ -4088,9 +4115,7 @@ static int slice_mismatch_impl(bmx_ctx* ctx, const bmx_vec* const* a, size_t na,
     OperandTable ops;
     if ((rc = operand_list(ctx, list.data(), list.size(), nullptr, 0, true, &ops))) return rc;
     const uint64_t size_hi = std::max(size_a, size_b), size_lo = first ? size_hi : std::min(size_a, size_b);
-    uint64_t nblocks64 = (size_hi + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    const uint32_t ncols = (uint32_t)nblocks64;
+    const uint32_t ncols = std::max(ca.ncols, cb.ncols);
     if (!P || !ncols) return result ? vec_all_null(ctx, size_hi, ncols, result) : BMX_OK;   // no planes at all / no rows: empty result, count 0, not found
     // the NULL term (bmx_kernels17.h); an absent side of the XOR is ones[0, fill)
     int null_mode = MM_NULL_NONE; uint64_t fill = 0;
@@ -4111,37 +4136,16 @@ static int slice_mismatch_impl(bmx_ctx* ctx, const bmx_vec* const* a, size_t na,
     hipLaunchKernelGGL(k_slice_mismatch, dim3(((c1) - (c0) + 3) / 4), dim3(256), 0, ctx->stream, \
                        ops.d_descs, ops.d_nblk, (u32)P, (u32)(c0), (u32)(c1), size_lo, size_hi, null_mode, fill, ending, ctx->xcd_swz, \
                        v ? v->d_bits : nullptr, v ? v->d_desc : nullptr, st, ctx->d_slots, ctx->d_small)
-    if (first) {
-        // the windows of find_first_impl, all enqueued at once: a wave per column, first window = 2 waves per CU
-        hipError_t e = hipMemsetAsync(ctx->d_small, 0xFF, 8, ctx->stream);
-        if (e == hipSuccess)
-            rc = ff_windows(ctx, 0u, ncols, 512u, [&](u32 c0, u32 c1) {
-                MM_LAUNCH(c0, c1, MM_FIRST);
-                hipError_t le = hipGetLastError();
-                return le == hipSuccess ? BMX_OK : fail_hip(le, "k_slice_mismatch", __LINE__);
-            });
-        if (e == hipSuccess && !rc) e = hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (rc) return rc;
-        if (e != hipSuccess || e2 != hipSuccess) return fail_hip(e != hipSuccess ? e : e2, "bmx_slice_first_mismatch", __LINE__);
-        if (ctx->h_small[0] != ~0ull) { *found = 1; *idx = ctx->h_small[0]; }
-        return BMX_OK;
-    }
+    if (first)                                              // the windows of find_first_impl: a wave per column, first window = 2 waves per CU
+        return first_hit_run(ctx, "bmx_slice_first_mismatch", 0u, ncols, 512u, [&](u32 c0, u32 c1) {
+            MM_LAUNCH(c0, c1, MM_FIRST);
+            const hipError_t le = hipGetLastError();
+            return le == hipSuccess ? BMX_OK : fail_hip(le, "k_slice_mismatch", __LINE__);
+        }, found, idx);
     MM_LAUNCH(0u, ncols, result ? MM_STORE : MM_COUNT);
 #undef MM_LAUNCH
     KCHK();
-    if (!result) {
-        hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(64), 0, ctx->stream, ctx->d_slots, ctx->d_small);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(ctx->h_small, ctx->d_small, 8, hipMemcpyDeviceToHost, ctx->stream));
-    } else if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    d_tab.reset();                                          // (before the count pass below allocates)
-    if (result) {
-        *result = v.release();
-        if (count) { rc = bmx_count(ctx, *result, count); if (rc) return rc; }
-    } else *count = ctx->h_small[0];
-    return BMX_OK;
+    return vec_or_count_tail(ctx, v, st, offs, d_tab, result, count);
 }
 
 int bmx_slice_mismatch(bmx_ctx* ctx, const bmx_vec* const* a, size_t na, uint64_t size_a, const bmx_vec* not_null_a,
@@ -4166,16 +4170,14 @@ struct SliceValues {
     uint32_t ncols = 0, P = 0; uint64_t size = 0, total = 0;
     explicit SliceValues(bmx_ctx* ctx) : d_tab(ctx), d_cnt(ctx), d_start(ctx) {}
 };
-static int slice_values_count(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
-                              const bmx_vec* bv_in, SliceValues* sv)
+static int slice_values_count(bmx_ctx* ctx, const SliceColumn& col, const bmx_vec* bv_in, SliceValues* sv)
 {
     int rc;
-    uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    sv->ncols = (uint32_t)nblocks64; sv->P = (uint32_t)nslices; sv->size = size; sv->total = 0;
+    const size_t nslices = col.nmag; const uint64_t size = col.size;
+    sv->ncols = col.ncols; sv->P = (uint32_t)nslices; sv->size = size; sv->total = 0;
     std::vector<const bmx_vec*> list(nslices + 2, nullptr);
-    for (size_t i = 0; i < nslices; ++i) list[i] = slices[i];
-    list[nslices] = not_null; list[nslices + 1] = bv_in;
+    for (size_t i = 0; i < nslices; ++i) list[i] = col.mag[i];
+    list[nslices] = col.not_null; list[nslices + 1] = bv_in;
     if ((rc = operand_list(ctx, list.data(), list.size(), nullptr, 0, true, &sv->ops))) return rc;
     if (!sv->ncols) return BMX_OK;
     if ((rc = direct_table(ctx, &sv->ops, sv->d_tab)) || (rc = dmalloc(ctx, &sv->d_cnt.p, (size_t)sv->ncols * 4)) ||
@@ -4200,23 +4202,19 @@ static int slice_values_emit(bmx_ctx* ctx, const SliceValues& sv, int width, voi
     KCHK();
     return BMX_OK;
 }
-static int slice_values_args(const bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, int width)
-{
-    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && (width == 4 || width == 8));
-    if (width == 4 && nslices > 32) { g_last_error = "more than 32 planes do not fit 32-bit values: use width 8"; return BMX_ERR_BADARG; }
-    return BMX_OK;
-}
 
 static int slice_values_impl(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
                              const bmx_vec* bv_in, int width, void* values, void* rows, bool host, uint64_t cap, uint64_t* n)
 {
-    int rc = slice_values_args(ctx, slices, nslices, width); if (rc) return rc;
-    ARGCHK(n && (cap == 0 || values));
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, 64, false, size, not_null, &col, SLICE_OTHER_CTX); if (rc) return rc;
+    ARGCHK((width == 4 || width == 8) && n && (cap == 0 || values));
+    if (width == 4 && nslices > 32) { g_last_error = "more than 32 planes do not fit 32-bit values: use width 8"; return BMX_ERR_BADARG; }
     *n = 0;
     if ((rc = set_dev(ctx))) return rc;
     if (rows && width == 4 && size > (1ull << 32)) { g_last_error = "32-bit row ids cannot address this column: use width 8"; return BMX_ERR_RANGE; }
     SliceValues sv(ctx);
-    if ((rc = slice_values_count(ctx, slices, nslices, size, not_null, bv_in, &sv))) return rc;
+    if ((rc = slice_values_count(ctx, col, bv_in, &sv))) return rc;
     *n = sv.total;
     if (sv.total > cap) { g_last_error = "output buffer too small for the values (n holds the number needed)"; return BMX_ERR_RANGE; }
     if (!sv.total) return BMX_OK;
@@ -4255,14 +4253,15 @@ int bmx_slice_remap(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, 
     *result = nullptr;
     if (n_rows) *n_rows = 0;
     const int width = nslices > 32 ? 8 : 4;
-    int rc = slice_values_args(ctx, slices, nslices, width); if (rc) return rc;
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, 64, false, size, not_null, &col, SLICE_OTHER_CTX); if (rc) return rc;
     if (nbits_out > (uint64_t)IDS_MAX_BLOCKS * BMX_BLOCK_BITS) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
     if ((rc = set_dev(ctx))) return rc;
     DevBuf d_val(ctx);
     uint64_t n = 0;
     {
         SliceValues sv(ctx);
-        if ((rc = slice_values_count(ctx, slices, nslices, size, not_null, bv_in, &sv))) return rc;
+        if ((rc = slice_values_count(ctx, col, bv_in, &sv))) return rc;
         n = sv.total;
         if (n > 0xFFFFFFFFull) { g_last_error = "more than 2^32 - 1 selected rows in one call"; return BMX_ERR_RANGE; }
         if (n && ((rc = dmalloc(ctx, &d_val.p, (size_t)n * (size_t)width)) || (rc = slice_values_emit(ctx, sv, width, d_val.p, nullptr)))) return rc;
@@ -4272,6 +4271,88 @@ int bmx_slice_remap(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, 
     return BMX_OK;
 ABI_END }
 
+// ---- the plane table of the kernels that walk raw planes (k_slice_eq_counts*, k_slice_eq_keys, k_slice_le_counts) ----
+// Those kernels decode no GAP block: an operand that holds one is expanded to raw words (k_vec_expand) over the window of
+// block columns the launches behind it cover; the others are read through their descriptor tables.
+struct PlaneTable {
+    std::vector<const bmx_vec*> ops;                        // planes, then what else the caller lists (sign, not-NULL); null = absent
+    std::vector<const uint4*> raw;                          // per operand: its raw words over the window, null where it holds no GAP block
+    DevBuf buf;                                             // ... all in one pooled block: ngap operands x wcols columns x 8 KiB
+    size_t ngap = 0; u32 wcols = 0;
+    explicit PlaneTable(bmx_ctx* ctx) : buf(ctx) {}
+};
+static PlaneTable plane_table(bmx_ctx* ctx, const bmx_vec* const* planes, size_t n, std::initializer_list<const bmx_vec*> more = {})
+{
+    PlaneTable t(ctx);
+    if (n) t.ops.assign(planes, planes + n);
+    t.ops.insert(t.ops.end(), more);
+    t.raw.assign(t.ops.size(), nullptr);
+    for (const bmx_vec* v : t.ops) if (v && v->counts[BMX_GAP]) ++t.ngap;
+    return t;
+}
+// raw words of block columns [c0, c1) of every GAP-holding operand, enqueued; the first call takes the block, as many columns
+// per operand as its window has: a later window may be shorter, never longer
+static int plane_table_expand(bmx_ctx* ctx, PlaneTable& t, u32 c0, u32 c1)
+{
+    const u32 wn = c1 - c0;
+    if (!t.ngap) return BMX_OK;
+    if (!t.buf.p) {
+        t.wcols = wn;
+        const int rc = dmalloc(ctx, &t.buf.p, t.ngap * (size_t)wn * 8192); if (rc) return rc;
+        size_t g = 0;
+        for (size_t i = 0; i < t.ops.size(); ++i)
+            if (t.ops[i] && t.ops[i]->counts[BMX_GAP]) t.raw[i] = (const uint4*)t.buf + g++ * (size_t)wn * 512u;
+    }
+    assert(wn <= t.wcols);
+    for (size_t i = 0; i < t.ops.size(); ++i) {
+        const bmx_vec* v = t.ops[i];
+        if (!t.raw[i]) continue;
+        const u32 rem = v->nblocks > c0 ? v->nblocks - c0 : 0u;
+        hipLaunchKernelGGL(k_vec_expand, dim3((wn + 3) / 4), dim3(256), 0, ctx->stream, rem ? v->d_desc + c0 : v->d_desc, rem, wn, (uint4*)t.raw[i]);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail_hip(e, "k_vec_expand", __LINE__);
+    }
+    return BMX_OK;
+}
+// the rows of the table as a kernel declares them: put(i, descriptor table or null, raw words or null, blocks) per present operand
+extern "C++" { template <class Put> static void plane_rows(const PlaneTable& t, Put&& put)
+{
+    for (size_t i = 0; i < t.ops.size(); ++i)
+        if (const bmx_vec* v = t.ops[i]) put(i, t.raw[i] ? nullptr : (const u64*)v->d_desc, t.raw[i], v->nblocks);
+} }
+
+// The two table forms of bmx_slice_eq_counts, built on the host from one pass's unique values: the blob the kernel reads, the
+// number of 64-bit counters it adds into, and the counter each value landed at (`where` empty: counter k is value k's).
+struct EqTable { std::vector<uint32_t> blob, where; uint32_t tab = 0, shift = 0; size_t ncount = 0; };
+// up to 2,048 values: open addressing, [keys u32 x tab][ordinals u16 x tab]; a counter per value
+static EqTable eq_table_ordinals(const uint32_t* vals, uint32_t nv)
+{
+    EqTable t;
+    t.tab = 64; while (t.tab < 2u * nv) t.tab <<= 1;
+    t.shift = 32; for (uint32_t s = t.tab; s > 1; s >>= 1) --t.shift;
+    t.blob.assign(t.tab + t.tab / 2, 0); t.ncount = nv;
+    uint32_t* keys = t.blob.data(); uint16_t* idx = reinterpret_cast<uint16_t*>(t.blob.data() + t.tab);
+    for (uint32_t k = 0; k < nv; ++k) {
+        uint32_t v = vals[k], h = (v * 0x9E3779B1u) >> t.shift;
+        while (keys[h]) h = (h + 1u) & (t.tab - 1u);
+        keys[h] = v; idx[h] = (uint16_t)k;
+    }
+    return t;
+}
+// more: the lean table, keys only, EQB_SLOTS(nv) slots; a counter per slot
+static EqTable eq_table_lean(const uint32_t* vals, uint32_t nv)
+{
+    EqTable t;
+    t.tab = EQB_SLOTS(nv);
+    t.blob.assign(t.tab, 0); t.where.resize(nv); t.ncount = t.tab;
+    for (uint32_t k = 0; k < nv; ++k) {
+        uint32_t v = vals[k], h = (uint32_t)(((uint64_t)(uint32_t)(v * 0x9E3779B1u) * t.tab) >> 32);
+        while (t.blob[h]) h = h + 1u == t.tab ? 0u : h + 1u;
+        t.blob[h] = v; t.where[k] = h;
+    }
+    return t;
+}
+
 // counts[q] = rows equal to values[q]: one pass over the planes whatever the number of queries (k_slice_eq_counts:
 // bit-matrix transposition + hash lookup); identical to the per-query AND-SUB groups of the reference
 // (src/bmsparsevec_algo.h:2593-2640).  Value 0 goes through bmx_slice_compare (NULL correction); a value with a bit
@@ -4279,19 +4360,15 @@ ABI_END }
 int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* values, size_t n,
                         uint64_t size, const bmx_vec* not_null, uint64_t* counts)
 { ABI_TRY
-    ARGCHK(ctx && (nslices == 0 || slices) && (n == 0 || (values && counts)));
-    ARGCHK(!not_null || not_null->ctx == ctx);
     if (nslices > 32) { g_last_error = "more than 32 planes: use the pipeline form (bmx_pipeline_*)"; return BMX_ERR_RANGE; }
-    int rc = set_dev(ctx); if (rc) return rc;
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, 32, false, size, not_null, &col); if (rc) return rc;
+    ARGCHK(n == 0 || (values && counts));
+    if ((rc = set_dev(ctx))) return rc;
     for (size_t q = 0; q < n; ++q) counts[q] = 0;
-    uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    const uint32_t ncols = (uint32_t)nblocks64;
+    const uint32_t ncols = col.ncols;
     uint32_t present = 0;
-    for (size_t i = 0; i < nslices; ++i) if (slices[i]) {
-        if (slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-        present |= 1u << i;
-    }
+    for (size_t i = 0; i < nslices; ++i) if (slices[i]) present |= 1u << i;
     // unique non-zero values that can match at all; value 0 through the comparison kernel
     std::vector<uint32_t> uniq; std::vector<int64_t> slot(n, -1);
     {
@@ -4310,24 +4387,11 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
         }
     }
     if (uniq.empty() || !ncols) return BMX_OK;
-    // planes holding GAP blocks are expanded to raw bits once (k_vec_expand); the others are read through their tables
+    // planes holding GAP blocks are expanded to raw bits once (the whole column is the window); the others are read through their tables
+    PlaneTable pt = plane_table(ctx, slices, nslices);
+    if ((rc = plane_table_expand(ctx, pt, 0u, ncols))) return rc;
     EqPlanes pl; memset(&pl, 0, sizeof(pl));
-    std::vector<DevBuf> bufs;
-    bufs.reserve(nslices);
-    for (size_t i = 0; i < nslices; ++i) {
-        const bmx_vec* sv = slices[i];
-        if (!sv) continue;
-        pl.nblk[i] = sv->nblocks;
-        if (sv->counts[BMX_GAP]) {
-            bufs.emplace_back(ctx);
-            if ((rc = dmalloc(ctx, &bufs.back().p, (size_t)ncols * 8192))) return rc;
-            const uint4* raw = (const uint4*)bufs.back();
-            hipLaunchKernelGGL(k_vec_expand, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, sv->d_desc, sv->nblocks, ncols, (uint4*)raw);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return fail_hip(e, "k_vec_expand", __LINE__); }
-            pl.raw[i] = raw;
-        } else pl.desc[i] = sv->d_desc;
-    }
+    plane_rows(pt, [&](size_t i, const u64* desc, const uint4* raw, u32 nblk) { pl.desc[i] = desc; pl.raw[i] = raw; pl.nblk[i] = nblk; });
     std::vector<uint64_t> ucount(uniq.size(), 0);
     // up to 2,048 values: the table with ordinals (2 workgroups per CU); more: the lean {key, count} table shared by 512
     // threads, up to EQB_MAX_VALUES per pass over the planes (eq_big: 0 = never, 1 = always, -1 = by the batch size)
@@ -4335,79 +4399,46 @@ int bmx_slice_eq_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
     // automatic: the lean table with 768 threads for every batch over more than 16 planes; up to 16 planes (dense value
     // spaces: most rows are looked up) the 2,048-value kernel keeps batches it can take in one pass (2.33 vs 2.86 ms)
     const bool big = (ctx->eq_big == 1 || (ctx->eq_big < 0 && uniq.size() > ((ctx->eq_big_shape == 2 && nslices > 16) ? 0u : 2048u))) && ctx->max_lds_bytes >= EQB_SLOTS(EQB_MAX_VALUES) * 8u + (1u << 15) + 8u * 512u * 4u;
-    const size_t cap = big ? (ctx->eq_big_shape == 2 ? 8704u : EQB_MAX_VALUES) : 2048;       // (768 threads: 24 KiB of queues)
-    const size_t npass = (uniq.size() + cap - 1) / cap;
-    const size_t CHUNK = (uniq.size() + npass - 1) / npass;
-    for (size_t u0 = 0; u0 < uniq.size() && !rc; u0 += CHUNK) {
-        const uint32_t nv = (uint32_t)std::min(CHUNK, uniq.size() - u0);
-        if (big) {
-            const uint32_t tab = EQB_SLOTS(nv);
-            std::vector<uint32_t> keys(tab, 0), where(nv);
-            for (uint32_t k = 0; k < nv; ++k) {
-                uint32_t v = uniq[u0 + k], h = (uint32_t)(((uint64_t)(uint32_t)(v * 0x9E3779B1u) * tab) >> 32);
-                while (keys[h]) h = h + 1u == tab ? 0u : h + 1u;
-                keys[h] = v; where[k] = h;
-            }
-            DevBuf d_tab(ctx), d_cnt(ctx);
-            if ((rc = dmalloc(ctx, &d_tab.p, (size_t)tab * 4)) || (rc = dmalloc(ctx, &d_cnt.p, (size_t)tab * 8))) break;
-            std::vector<uint64_t> scount(tab, 0);
-            rc = h2d_staged(ctx, d_tab.p, keys.data(), (size_t)tab * 4);
-            hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt.p, 0, (size_t)tab * 8, ctx->stream);
-            if (!rc && e == hipSuccess) {
-                // eq_big_shape: 0 = 512 threads, 16 KiB filter, 1,024-entry queues; 1 = 512 threads, 32 KiB filter, 512-entry queues;
-                // 2 = 768 threads with the registers held to 3 waves per SIMD (8 filter reads in flight instead of 32), 32 KiB + 512
-                const int shp = ctx->eq_big_shape;
-                const u32 wg = shp == 2 ? 768u : 512u, nw = wg / 64u;
-                size_t lds = (size_t)tab * 8 + (shp >= 1 ? (1u << 15) + nw * 512u * 4u : (1u << 14) + nw * 1024u * 4u);
-                auto eqfn = shp == 2 ? (nslices <= 16 ? k_slice_eq_counts_big<16, 18, 512, 768, 3, 8> : k_slice_eq_counts_big<32, 18, 512, 768, 3, 4>)   /* (32 planes: 4 filter reads in flight -- 8 need 3 VGPRs more than three waves per SIMD leave: 12 B of scratch) */
-                          : shp == 1 ? (nslices <= 16 ? k_slice_eq_counts_big<16, 18, 512> : k_slice_eq_counts_big<32, 18, 512>)
-                                     : (nslices <= 16 ? k_slice_eq_counts_big<16, 17, 1024> : k_slice_eq_counts_big<32, 17, 1024>);
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(eqfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess) {
-                    u32 grid = std::min<u32>((ncols + nw - 1u) / nw, 256u);
-                    hipLaunchKernelGGL(eqfn, dim3(grid), dim3(wg), lds, ctx->stream, pl, (u32)nslices, ncols, size, (const u32*)d_tab, tab, (u64*)d_cnt);
-                    e = hipGetLastError();
-                }
-                if (e == hipSuccess) e = hipMemcpyAsync(scount.data(), d_cnt.p, (size_t)tab * 8, hipMemcpyDeviceToHost, ctx->stream);
-            }
-            hipError_t e2 = hipStreamSynchronize(ctx->stream);
-            d_tab.reset(); d_cnt.reset();
-            if (!rc && (e != hipSuccess || e2 != hipSuccess)) rc = fail_hip(e != hipSuccess ? e : e2, "bmx_slice_eq_counts", __LINE__);
-            if (!rc) for (uint32_t k = 0; k < nv; ++k) ucount[u0 + k] = scount[where[k]];
-            continue;
-        }
-        uint32_t tab = 64; while (tab < 2u * nv) tab <<= 1;
-        uint32_t shift = 32; for (uint32_t t = tab; t > 1; t >>= 1) --shift;
-        // host-built open-addressing table: [keys u32 x tab][idx u16 x tab]
-        std::vector<uint32_t> blob(tab + tab / 2, 0);
-        uint32_t* keys = blob.data(); uint16_t* idx = reinterpret_cast<uint16_t*>(blob.data() + tab);
-        for (uint32_t k = 0; k < nv; ++k) {
-            uint32_t v = uniq[u0 + k], h = (v * 0x9E3779B1u) >> shift;
-            while (keys[h]) h = (h + 1u) & (tab - 1u);
-            keys[h] = v; idx[h] = (uint16_t)k;
-        }
+    const u32 cap = big ? (ctx->eq_big_shape == 2 ? 8704u : EQB_MAX_VALUES) : 2048u;         // (768 threads: 24 KiB of queues)
+    const size_t per = even_windows((u32)uniq.size(), cap).per;
+    // setting the kernel's LDS size, then its launch over the planes; what follows the column's size in its arguments is the table's
+    auto launch = [&](auto fn, u32 grid, u32 wg, size_t lds, auto... table) -> hipError_t {
+        const hipError_t le = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (le != hipSuccess) return le;
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(wg), lds, ctx->stream, pl, (u32)nslices, ncols, size, table...);
+        return hipGetLastError();
+    };
+    for (size_t u0 = 0; u0 < uniq.size() && !rc; u0 += per) {
+        const uint32_t nv = (uint32_t)std::min(per, uniq.size() - u0);
+        const EqTable tb = big ? eq_table_lean(uniq.data() + u0, nv) : eq_table_ordinals(uniq.data() + u0, nv);
+        const uint32_t tab = tb.tab;
         DevBuf d_tab(ctx), d_cnt(ctx);
-        if ((rc = dmalloc(ctx, &d_tab.p, blob.size() * 4)) || (rc = dmalloc(ctx, &d_cnt.p, (size_t)nv * 8))) break;
-        rc = h2d_staged(ctx, d_tab.p, blob.data(), blob.size() * 4);
-        hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt.p, 0, (size_t)nv * 8, ctx->stream);
-        if (!rc && e == hipSuccess) {
-            size_t lds = (size_t)tab * 4 + (size_t)nv * 4 + EQ_FILTER_WORDS * 4 + 4 * EQ_QUEUE * 4 + (size_t)tab * 2;
-            auto eqfn = nslices <= 16 ? k_slice_eq_counts<16> : k_slice_eq_counts<32>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(eqfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) {
-                u32 grid = std::min<u32>((ncols + 3u) / 4u, 512u);
-                hipLaunchKernelGGL(eqfn, dim3(grid), dim3(256), lds, ctx->stream, pl, (u32)nslices, ncols, size,
-                                   (const u32*)d_tab, (const u16*)((const u32*)d_tab + tab), tab, shift, nv, (u64*)d_cnt);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(ucount.data() + u0, d_cnt.p, (size_t)nv * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if ((rc = dmalloc(ctx, &d_tab.p, tb.blob.size() * 4)) || (rc = dmalloc(ctx, &d_cnt.p, tb.ncount * 8))) break;
+        std::vector<uint64_t> scount(tb.where.empty() ? 0 : tb.ncount, 0);
+        uint64_t* const h_cnt = tb.where.empty() ? ucount.data() + u0 : scount.data();   // counters in value order land where they belong
+        rc = h2d_staged(ctx, d_tab.p, tb.blob.data(), tb.blob.size() * 4);
+        hipError_t e = rc ? hipSuccess : hipMemsetAsync(d_cnt.p, 0, tb.ncount * 8, ctx->stream);
+        if (!rc && e == hipSuccess && big) {
+            // eq_big_shape: 0 = 512 threads, 16 KiB filter, 1,024-entry queues; 1 = 512 threads, 32 KiB filter, 512-entry queues;
+            // 2 = 768 threads with the registers held to 3 waves per SIMD (8 filter reads in flight instead of 32), 32 KiB + 512
+            const int shp = ctx->eq_big_shape;
+            const u32 wg = shp == 2 ? 768u : 512u, nw = wg / 64u;
+            const size_t lds = (size_t)tab * 8 + (shp >= 1 ? (1u << 15) + nw * 512u * 4u : (1u << 14) + nw * 1024u * 4u);
+            auto eqfn = shp == 2 ? (nslices <= 16 ? k_slice_eq_counts_big<16, 18, 512, 768, 3, 8> : k_slice_eq_counts_big<32, 18, 512, 768, 3, 4>)   /* (32 planes: 4 filter reads in flight -- 8 need 3 VGPRs more than three waves per SIMD leave: 12 B of scratch) */
+                      : shp == 1 ? (nslices <= 16 ? k_slice_eq_counts_big<16, 18, 512> : k_slice_eq_counts_big<32, 18, 512>)
+                                 : (nslices <= 16 ? k_slice_eq_counts_big<16, 17, 1024> : k_slice_eq_counts_big<32, 17, 1024>);
+            e = launch(eqfn, std::min<u32>((ncols + nw - 1u) / nw, 256u), wg, lds, (const u32*)d_tab, tab, (u64*)d_cnt);
+        } else if (!rc && e == hipSuccess) {
+            const size_t lds = (size_t)tab * 4 + (size_t)nv * 4 + EQ_FILTER_WORDS * 4 + 4 * EQ_QUEUE * 4 + (size_t)tab * 2;
+            e = launch(nslices <= 16 ? k_slice_eq_counts<16> : k_slice_eq_counts<32>, std::min<u32>((ncols + 3u) / 4u, 512u), 256u, lds,
+                       (const u32*)d_tab, (const u16*)((const u32*)d_tab + tab), tab, tb.shift, nv, (u64*)d_cnt);
         }
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        d_tab.reset(); d_cnt.reset();
+        if (!rc && e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt.p, tb.ncount * 8, hipMemcpyDeviceToHost, ctx->stream);
+        const hipError_t e2 = hipStreamSynchronize(ctx->stream);         // (on every path: h_cnt may have a copy coming)
         if (!rc && (e != hipSuccess || e2 != hipSuccess)) rc = fail_hip(e != hipSuccess ? e : e2, "bmx_slice_eq_counts", __LINE__);
+        if (!rc) for (size_t k = 0; k < tb.where.size(); ++k) ucount[u0 + k] = scount[tb.where[k]];
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    bufs.clear();
+    (void)hipStreamSynchronize(ctx->stream);                 // (idle after a completed pass; after a failed allocation the expansions are still running)
     if (rc) return rc;
     for (size_t q = 0; q < n; ++q) if (slot[q] >= 0) counts[q] = ucount[(size_t)slot[q]];
     return BMX_OK;
@@ -4443,21 +4474,16 @@ static int eqk_zero_key(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslic
 int bmx_slice_eq_keys(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, uint64_t size, const bmx_vec* not_null,
                       const uint8_t* keys, size_t key_bytes, size_t n, uint64_t* counts, uint64_t* first, uint8_t* found)
 { ABI_TRY
-    ARGCHK(ctx && (nslices == 0 || slices));
-    ARGCHK(!not_null || not_null->ctx == ctx);
-    ARGCHK(n == 0 || (keys && (counts || first || found)));
     if (nslices > BMX_EQK_MAX_PLANES) { g_last_error = "more than BMX_EQK_MAX_PLANES planes"; return BMX_ERR_RANGE; }
-    const uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    const uint32_t ncols = (uint32_t)nblocks64;
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, BMX_EQK_MAX_PLANES, false, size, not_null, &col); if (rc) return rc;
+    ARGCHK(n == 0 || (keys && (counts || first || found)));
+    const uint32_t ncols = col.ncols;
     const uint32_t T = (uint32_t)((nslices + 31) / 32);
     std::vector<uint32_t> present(T, 0u);
-    for (size_t i = 0; i < nslices; ++i) if (slices[i]) {
-        if (slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-        present[i >> 5] |= 1u << (i & 31);
-    }
+    for (size_t i = 0; i < nslices; ++i) if (slices[i]) present[i >> 5] |= 1u << (i & 31);
     if (!n) return BMX_OK;
-    int rc = set_dev(ctx); if (rc) return rc;
+    if ((rc = set_dev(ctx))) return rc;
     for (size_t q = 0; q < n; ++q) { if (counts) counts[q] = 0; if (first) first[q] = 0; if (found) found[q] = 0; }
     // distinct non-zero keys that can match at all, as T words each (bit b of octet j = plane 8 j + b); a key with a bit at or
     // beyond nslices or in an absent plane matches nothing (:2569); the all-zero key goes through the aggregator
@@ -4510,7 +4536,7 @@ int bmx_slice_eq_keys(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices
     // every pass's table: [fingerprints: tab][keys: tab x T]; slot numbers run on across the passes
     struct Pass { size_t u0; uint32_t nv, tab; size_t blob_off, slot0; };
     std::vector<Pass> passes;
-    const size_t npass = (nu + cap - 1) / cap, chunk = (nu + npass - 1) / npass;
+    const size_t chunk = even_windows((u32)nu, cap).per;
     size_t blob_words = 0, nslots = 0;
     for (size_t u0 = 0; u0 < nu; u0 += chunk) {
         const uint32_t nv = (uint32_t)std::min(chunk, nu - u0), tab = EQK_SLOTS(nv);
@@ -4535,19 +4561,17 @@ int bmx_slice_eq_keys(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices
     }
     // GAP-holding planes are expanded to raw bits a window of block columns at a time ("eqk_expand_kb"): counts add and firsts
     // take the minimum across windows (the per-slot arrays stay on the device until the last window)
-    std::vector<size_t> gap_planes;
-    for (size_t i = 0; i < nslices; ++i) if (slices[i] && slices[i]->counts[BMX_GAP]) gap_planes.push_back(i);
+    PlaneTable pt = plane_table(ctx, slices, nslices);
     uint32_t wcols = ncols;
-    if (!gap_planes.empty()) {
-        const uint64_t per_col = (uint64_t)gap_planes.size() * 8192u;
+    if (pt.ngap) {
+        const uint64_t per_col = (uint64_t)pt.ngap * 8192u;
         wcols = (uint32_t)std::min<uint64_t>(ncols, std::max<uint64_t>(1, (uint64_t)ctx->eqk_expand_kb * 1024u / per_col));
     }
-    DevBuf d_raw(ctx), d_planes(ctx), d_blob(ctx), d_res(ctx);
-    if (!gap_planes.empty() && (rc = dmalloc(ctx, &d_raw.p, (size_t)gap_planes.size() * wcols * 8192u))) return rc;
+    if ((rc = plane_table_expand(ctx, pt, 0u, wcols))) return rc;        // the first window: it sizes the raw buffers the rows point at
+    DevBuf d_planes(ctx), d_blob(ctx), d_res(ctx);
     std::vector<EqkPlane> hpl(nslices);
     memset(hpl.data(), 0, hpl.size() * sizeof(EqkPlane));
-    for (size_t i = 0; i < nslices; ++i) if (slices[i]) { hpl[i].desc = slices[i]->d_desc; hpl[i].nblk = slices[i]->nblocks; }
-    for (size_t g = 0; g < gap_planes.size(); ++g) hpl[gap_planes[g]].raw = (const uint4*)d_raw + g * (size_t)wcols * 512u;
+    plane_rows(pt, [&](size_t i, const u64* desc, const uint4* raw, u32 nblk) { hpl[i].desc = desc; hpl[i].raw = raw; hpl[i].nblk = nblk; });
     if ((rc = dmalloc(ctx, &d_planes.p, hpl.size() * sizeof(EqkPlane))) || (rc = dmalloc(ctx, &d_blob.p, blob_words * 4)) ||
         (rc = dmalloc(ctx, &d_res.p, nslots * 16))) return rc;
     u64* d_cnt = (u64*)d_res; u64* d_first = d_cnt + nslots;
@@ -4562,13 +4586,7 @@ int bmx_slice_eq_keys(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices
     if (!rc && e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_slice_eq_keys), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
     for (uint32_t c0 = 0; c0 < ncols && !rc && e == hipSuccess; c0 += wcols) {
         const uint32_t c1 = std::min(ncols, c0 + wcols), wn = c1 - c0;
-        for (size_t g = 0; g < gap_planes.size() && e == hipSuccess; ++g) {
-            const bmx_vec* sv = slices[gap_planes[g]];
-            const uint32_t rem = sv->nblocks > c0 ? sv->nblocks - c0 : 0u;
-            hipLaunchKernelGGL(k_vec_expand, dim3((wn + 3) / 4), dim3(256), 0, ctx->stream, rem ? sv->d_desc + c0 : sv->d_desc, rem, wn,
-                               (uint4*)d_raw + g * (size_t)wcols * 512u);
-            e = hipGetLastError();
-        }
+        if (c0 && (rc = plane_table_expand(ctx, pt, c0, c1))) break;
         for (size_t i = 0; i < passes.size() && e == hipSuccess; ++i) {
             const Pass& p = passes[i];
             const u32* d_fp = (const u32*)d_blob + p.blob_off;
@@ -4665,50 +4683,35 @@ static int le_counts_launch(bmx_ctx* ctx, const LeOperand* d_ops, u32 nmag, u32 
     return e == hipSuccess ? BMX_OK : fail_hip(e, "k_slice_le_counts", __LINE__);
 }
 
-// shared body: mag = the magnitude planes, sign = the sign plane of a signed container (or null)
-static int range_counts_impl(bmx_ctx* ctx, const bmx_vec* const* mag, size_t nmag, const bmx_vec* sign, bool sgn,
-                             const uint64_t* lo, const uint64_t* hi, size_t n, uint64_t size, const bmx_vec* not_null, uint64_t* counts,
-                             uint64_t* plane_bytes = nullptr, uint32_t* launches = nullptr)
+// the batched path over a checked column; sgn: col.sign is the sign plane of a signed container, lo / hi hold int64_t bit patterns
+static int range_counts_impl(bmx_ctx* ctx, const SliceColumn& col, bool sgn, const uint64_t* lo, const uint64_t* hi, size_t n, uint64_t* counts,
+                             uint64_t* plane_bytes, uint32_t* launches)
 {
     if (plane_bytes) *plane_bytes = 0;
     if (launches) *launches = 0;
     int rc = set_dev(ctx); if (rc) return rc;
-    const uint64_t nblocks64 = (size + BMX_BLOCK_BITS - 1) / BMX_BLOCK_BITS;
-    if (nblocks64 > 65536ull * 16) { g_last_error = "vector too long"; return BMX_ERR_RANGE; }
-    const uint32_t ncols = (uint32_t)nblocks64;
+    const uint32_t ncols = col.ncols; const size_t nmag = col.nmag;
     const RangePlan plan = range_plan(lo, hi, n, sgn, nmag);
     const size_t NC = sgn ? 2 : 1, K = plan.thr.size();
     std::vector<uint64_t> res(3 + NC * K, 0);                            // [0], [1]: valid rows per sign class; [2]: bytes loaded; then LE per threshold (x NC)
     if (ncols) {
+        // rows: the magnitude planes, the sign plane, the not-NULL vector (bmx_kernels18.h); the whole column is the window
+        PlaneTable pt = plane_table(ctx, col.mag, nmag, {col.sign, col.not_null});
         std::vector<LeOperand> ops(nmag + 2);
         memset(ops.data(), 0, ops.size() * sizeof(LeOperand));
-        std::vector<DevBuf> bufs;
-        bufs.reserve(nmag + 2);
         DevBuf d_ops(ctx), d_cnt(ctx);
         auto enqueue = [&]() -> int {
             int r;
-            // operands holding GAP blocks are expanded to raw words once (bmx_kernels18.h); the others are read through their tables
-            for (size_t i = 0; i < nmag + 2; ++i) {
-                const bmx_vec* v = i < nmag ? mag[i] : (i == nmag ? sign : not_null);
-                if (!v) continue;
-                ops[i].nblk = v->nblocks;
-                if (!v->counts[BMX_GAP]) { ops[i].desc = v->d_desc; continue; }
-                bufs.emplace_back(ctx);
-                if ((r = dmalloc(ctx, &bufs.back().p, (size_t)ncols * 8192))) return r;
-                ops[i].raw = (const uint4*)bufs.back();
-                hipLaunchKernelGGL(k_vec_expand, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, v->d_desc, v->nblocks, ncols, (uint4*)bufs.back());
-                const hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return fail_hip(e, "k_vec_expand", __LINE__);
-            }
+            if ((r = plane_table_expand(ctx, pt, 0u, ncols))) return r;
+            plane_rows(pt, [&](size_t i, const u64* desc, const uint4* raw, u32 nblk) { ops[i].desc = desc; ops[i].raw = raw; ops[i].nblk = nblk; });
             if ((r = dmalloc(ctx, &d_ops.p, ops.size() * sizeof(LeOperand))) || (r = h2d_staged(ctx, d_ops.p, ops.data(), ops.size() * sizeof(LeOperand)))) return r;
             if ((r = dmalloc(ctx, &d_cnt.p, res.size() * 8))) return r;
             HIPCHK(hipMemsetAsync(d_cnt.p, 0, res.size() * 8, ctx->stream));
             // ceil(K / T) launches of about equal size, all enqueued before the one synchronisation; the first reports the valid rows
-            const size_t cap = ctx->rc_batch > 0 ? (size_t)ctx->rc_batch : (size_t)BMX_RC_BATCH_MAX;
-            const size_t npass = std::max<size_t>((K + cap - 1) / cap, 1), per = (K + npass - 1) / npass;
-            for (size_t p = 0, k0 = 0; p < npass; ++p, k0 += per) {
-                const u32 nthr = (u32)std::min(per, K - std::min(K, k0));
-                if ((r = le_counts_launch(ctx, (const LeOperand*)d_ops, (u32)nmag, ncols, sgn, plan.thr.data() + std::min(K, k0), nthr, size, not_null ? 1 : 0,
+            const Windows win = even_windows((u32)K, ctx->rc_batch > 0 ? (u32)ctx->rc_batch : (u32)BMX_RC_BATCH_MAX);
+            for (size_t p = 0, k0 = 0; p < win.nwin; ++p, k0 += win.per) {
+                const u32 nthr = (u32)std::min<size_t>(win.per, K - std::min(K, k0));
+                if ((r = le_counts_launch(ctx, (const LeOperand*)d_ops, (u32)nmag, ncols, sgn, plan.thr.data() + std::min(K, k0), nthr, col.size, col.not_null ? 1 : 0,
                                           (u64*)d_cnt + 3 + NC * std::min(K, k0), p == 0 ? (u64*)d_cnt : nullptr, plane_bytes ? (u64*)d_cnt + 2 : nullptr))) return r;
                 if (launches) ++*launches;
             }
@@ -4716,8 +4719,7 @@ static int range_counts_impl(bmx_ctx* ctx, const bmx_vec* const* mag, size_t nma
             return BMX_OK;
         };
         rc = enqueue();
-        const hipError_t e = hipStreamSynchronize(ctx->stream);          // (also on an error: nothing enqueued may outlive the buffers)
-        bufs.clear(); d_ops.reset(); d_cnt.reset();
+        const hipError_t e = hipStreamSynchronize(ctx->stream);          // (also on an error: res may have a copy coming)
         if (rc) return rc;
         if (e != hipSuccess) return fail_hip(e, "bmx_slice_range_counts", __LINE__);
     }
@@ -4730,53 +4732,43 @@ static int range_counts_impl(bmx_ctx* ctx, const bmx_vec* const* mag, size_t nma
     return BMX_OK;
 }
 
+// shared body of the three entries: the column's checks, then the comparison path -- one pass over the planes per range --
+// where the policy asks for it (never for the _stat entry, `batched`), else the batched path.  Signed: slices[0] = the sign plane.
+static int range_counts_entry(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, bool sgn, const uint64_t* lo, const uint64_t* hi, size_t n,
+                              uint64_t size, const bmx_vec* not_null, uint64_t* counts, bool batched, uint64_t* plane_bytes, uint32_t* launches)
+{
+    SliceColumn col;
+    int rc = slice_column(ctx, slices, nslices, 64, sgn, size, not_null, &col); if (rc) return rc;
+    ARGCHK(n == 0 || (lo && hi && counts));
+    if (!n) return BMX_OK;
+    if (batched || ctx->rc_batch > 0 || (ctx->rc_batch == 0 && n >= RC_LOOP_BELOW))
+        return range_counts_impl(ctx, col, sgn, lo, hi, n, counts, plane_bytes, launches);
+    for (size_t q = 0; q < n && !rc; ++q)
+        rc = sgn ? bmx_slice_compare_signed(ctx, slices, nslices, BMX_CMP_RANGE, (int64_t)lo[q], (int64_t)hi[q], size, not_null, nullptr, &counts[q])
+                 : bmx_slice_compare(ctx, slices, nslices, BMX_CMP_RANGE, lo[q], hi[q], size, not_null, nullptr, &counts[q]);
+    return rc;
+}
+
 extern "C" {
 
 int bmx_slice_range_counts(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* lo, const uint64_t* hi, size_t n,
                            uint64_t size, const bmx_vec* not_null, uint64_t* counts)
 { ABI_TRY
-    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && (n == 0 || (lo && hi && counts)));
-    ARGCHK(!not_null || not_null->ctx == ctx);
-    for (size_t i = 0; i < nslices; ++i)
-        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-    if (!n) return BMX_OK;
-    if (ctx->rc_batch < 0 || (ctx->rc_batch == 0 && n < RC_LOOP_BELOW)) {  // the comparison path: one pass over the planes per range
-        for (size_t q = 0; q < n; ++q) {
-            const int rc = bmx_slice_compare(ctx, slices, nslices, BMX_CMP_RANGE, lo[q], hi[q], size, not_null, nullptr, &counts[q]);
-            if (rc) return rc;
-        }
-        return BMX_OK;
-    }
-    return range_counts_impl(ctx, slices, nslices, nullptr, false, lo, hi, n, size, not_null, counts);
+    return range_counts_entry(ctx, slices, nslices, false, lo, hi, n, size, not_null, counts, false, nullptr, nullptr);
 ABI_END }
 
 int bmx_slice_range_counts_stat(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const uint64_t* lo, const uint64_t* hi, size_t n,
                                 uint64_t size, const bmx_vec* not_null, uint64_t* counts, uint64_t* plane_bytes, uint32_t* launches)
 { ABI_TRY
-    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 64 && n > 0 && lo && hi && counts && plane_bytes && launches);
-    ARGCHK(!not_null || not_null->ctx == ctx);
-    for (size_t i = 0; i < nslices; ++i)
-        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-    return range_counts_impl(ctx, slices, nslices, nullptr, false, lo, hi, n, size, not_null, counts, plane_bytes, launches);
+    ARGCHK(n > 0 && plane_bytes && launches);
+    return range_counts_entry(ctx, slices, nslices, false, lo, hi, n, size, not_null, counts, true, plane_bytes, launches);
 ABI_END }
 
 int bmx_slice_range_counts_signed(bmx_ctx* ctx, const bmx_vec* const* slices, size_t nslices, const int64_t* lo, const int64_t* hi, size_t n,
                                   uint64_t size, const bmx_vec* not_null, uint64_t* counts)
 { ABI_TRY
-    ARGCHK(ctx && (nslices == 0 || slices) && nslices <= 65 && (n == 0 || (lo && hi && counts)));
-    ARGCHK(!not_null || not_null->ctx == ctx);
-    for (size_t i = 0; i < nslices; ++i)
-        if (slices[i] && slices[i]->ctx != ctx) { g_last_error = "slice belongs to another context"; return BMX_ERR_BADARG; }
-    if (!n) return BMX_OK;
-    if (ctx->rc_batch < 0 || (ctx->rc_batch == 0 && n < RC_LOOP_BELOW)) {
-        for (size_t q = 0; q < n; ++q) {
-            const int rc = bmx_slice_compare_signed(ctx, slices, nslices, BMX_CMP_RANGE, lo[q], hi[q], size, not_null, nullptr, &counts[q]);
-            if (rc) return rc;
-        }
-        return BMX_OK;
-    }
-    return range_counts_impl(ctx, nslices ? slices + 1 : slices, nslices ? nslices - 1 : 0, nslices ? slices[0] : nullptr, true,
-                             reinterpret_cast<const uint64_t*>(lo), reinterpret_cast<const uint64_t*>(hi), n, size, not_null, counts);
+    return range_counts_entry(ctx, slices, nslices, true, reinterpret_cast<const uint64_t*>(lo), reinterpret_cast<const uint64_t*>(hi), n,
+                              size, not_null, counts, false, nullptr, nullptr);
 ABI_END }
 
 } // extern "C"

@@ -500,10 +500,50 @@ def test_device_allocation_failures_come_back_as_status(port):
         if first: assert "k_coll_members" in served[0].describe()        # (the path this family is about)
         c.set_tuning("coll_members", 1)
         return ok
+    # the bit-sliced scanner entries over two 8-plane columns: plane p of a column = vs[src[p]] (None: the plane is absent);
+    # vs[2:] hold GAP blocks (the entries that walk raw planes expand them first).  Expected values: a numpy column rebuilt
+    # from the same generated words, never the library
+    def bits_of(i, dq):
+        w = np.ascontiguousarray(port.gen_words(5, i, dq, nbits), np.uint32)
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[:nbits].astype(np.uint64)
+    vbits = [bits_of(i, dq) for i, dq in enumerate((6554, 655, 66, 66, 200, 66))]
+    def column(src):
+        col = np.zeros(nbits, np.uint64)
+        for p, i in enumerate(src):
+            if i is not None: col |= vbits[i] << np.uint64(p)
+        return col, [vs[i] if i is not None else None for i in src]
+    col_a, planes_a = column([0, 2, 1, None, 3, 4, 5, 2])
+    col_b, planes_b = column([0, 2, 1, None, 4, 3, 5, 2])
+    sc_a, sc_b = bm.slice_scanner(c, planes_a, size=nbits), bm.slice_scanner(c, planes_b, size=nbits)
+    exp_gt = np.flatnonzero(col_a > 37)
+    def scan_gt_vector(): return np.array_equal(sc_a.find_gt(37).to_indices(), exp_gt)
+    exp_range = int(((col_a >= 5) & (col_a <= 130)).sum())
+    def scan_range_count(): return sc_a.count(bm.CMP_RANGE, 5, 130) == exp_range
+    eq_vals = [0, 8, 1 << 9] + [int(v) for v in np.unique(col_a)[:40]] + [255, 247, 5, 5, 0, 1 << 40, 3]   # 0 twice, absent plane, above the planes
+    exp_eq = [int((col_a == np.uint64(v)).sum()) for v in eq_vals]
+    def scan_eq_counts(): return sc_a.find_eq_counts(eq_vals, method="transpose").tolist() == exp_eq
+    key_vals = [0, 5, 1, 8, 247, 1 << 9, 5]                              # the empty key, absent plane, a bit past the planes, a duplicate
+    keys = np.array([[v & 255, v >> 8] for v in key_vals], np.uint8)
+    hits = [np.flatnonzero(col_a == np.uint64(v)) for v in key_vals]
+    str_a = bm.str_scanner(c, planes_a, nbits)
+    def scan_eq_keys():
+        cnt, first, found = str_a.eq_keys(keys)
+        return (cnt.tolist() == [h.size for h in hits] and found.tolist() == [int(h.size > 0) for h in hits]
+                and first.tolist() == [int(h[0]) if h.size else 0 for h in hits])
+    rc_lo, rc_hi = [0, 10, 200], [9, 100, 255]
+    exp_rc = [int(((col_a >= lo) & (col_a <= hi)).sum()) for lo, hi in zip(rc_lo, rc_hi)]
+    def scan_range_counts(): return sc_a.find_range_counts(rc_lo, rc_hi).tolist() == exp_rc
+    exp_mm = np.flatnonzero(col_a != col_b)
+    exp_image = np.unique(col_a[vbits[4] != 0])
+    def scan_mismatch_remap():
+        ok = np.array_equal(bm.sparse_vector_find_mismatch(sc_a, sc_b, bm.NO_NULL).to_indices(), exp_mm)
+        return ok and np.array_equal(bm.set2set_11_transform(c).remap(vs[4], sc_a).to_indices(), exp_image)
     for name, fn in (("pairwise", pairwise), ("combine_or", combine_or), ("rs_index", rs_index), ("prepare", prepare), ("pipeline", pipeline),
                      ("pipeline_staged", pipeline_staged), ("pipeline_limit_dev", pipeline_limit_dev), ("op2_async", op2_async),
                      ("and_sub_materialised", and_sub_materialised), ("upload_gap", upload_gap), ("distance_gap", distance_gap),
-                     ("pipeline_coll_served", pipeline_coll_served)):
+                     ("pipeline_coll_served", pipeline_coll_served), ("scan_gt_vector", scan_gt_vector), ("scan_range_count", scan_range_count),
+                     ("scan_eq_counts", scan_eq_counts), ("scan_eq_keys", scan_eq_keys), ("scan_range_counts", scan_range_counts),
+                     ("scan_mismatch_remap", scan_mismatch_remap)):
         assert fn(), name                                 # warm: pooled blocks, scratch sized
         c.synchronize(); c.trim()
         base = c.mem_used()
