@@ -3345,12 +3345,15 @@ static int direct_launch(int mode, bmx_ctx* ctx, const OperandTable& t, size_t n
     return e == hipSuccess ? BMX_OK : fail_hip(e, "k_direct", __LINE__);
 }
 
-static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int opt_compress, bmx_vec** result);
-static bool coll_members_wanted_list(const bmx_ctx* ctx, const bmx_vec* const* src, size_t n)
+// ---- aggregator list calls (bmx_agg_or[_opt], bmx_agg_and_sub): a choice, one launch per path, one tail (list_finish) ----
+// ListPlan: the kernel path, the packed collection(s) and the lists' member indices; only agg_or_choose / agg_and_sub_choose read the thresholds
+enum ListPath { LP_NONE, LP_DIRECT, LP_MEMBERS, LP_COLL, LP_ROWS, LP_TILE, LP_SORT, LP_PIPELINE };
+struct ListPlan { ListPath path = LP_NONE; bmx_coll *a = nullptr, *s = nullptr; std::vector<u32> ma, ms; };
+static bool coll_members_wanted_list(const bmx_ctx* ctx, const bmx_vec* const* a, size_t na, const bmx_vec* const* b = nullptr, size_t nb = 0)
 {
     uint64_t gw = 0, gb = 0;
-    for (size_t i = 0; i < n; ++i) { gw += src[i]->gap_words; gb += src[i]->counts[BMX_GAP]; }
-    return coll_members_wanted(ctx, gw, gb, n, 1);
+    for (size_t i = 0; i < na + nb; ++i) { const bmx_vec* o = i < na ? a[i] : b[i - na]; gw += o->gap_words; gb += o->counts[BMX_GAP]; }
+    return coll_members_wanted(ctx, gw, gb, na + nb, 1);
 }
 
 // combine_or over >= 64 GAP-only operands: the row kernel (bmx_kernels7.h) when the operands are sparse enough for a tile of
@@ -3367,10 +3370,156 @@ static bool or_rows_wanted(const bmx_ctx* ctx, const bmx_vec* const* src, size_t
 {
     if (ctx->or_rows == 0) return false;
     uint64_t words = 0, blocks = 0;
-    for (size_t i = 0; i < n; ++i) {
-        words += src[i]->gap_words; blocks += src[i]->counts[BMX_GAP];
-    }
+    for (size_t i = 0; i < n; ++i) { words += src[i]->gap_words; blocks += src[i]->counts[BMX_GAP]; }
     return ctx->or_rows == 1 || (blocks && words * 10ull <= blocks * 328ull);     // <= 4.1 chunks of 8 words per GAP block
+}
+
+// The path of an OR list (ops: its operand_list).  With gap_pack 1 a list of >= 64 packable vectors is packed here at its first use.
+static int agg_or_choose(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, const OperandTable& ops, ListPlan* pl)
+{
+    const uint32_t ncols = ops.ncols;
+    if (use_direct(ctx, ncols, n)) { pl->path = LP_DIRECT; return BMX_OK; }
+    const bool gap_only = ncols && ops.has_gap && !ops.has_bit;
+    const bool rows = n >= 64 && gap_only && or_rows_wanted(ctx, src, n);
+    if (n >= 16 && gap_only) {
+        bool full = false;
+        if (int rc = coll_resolve(ctx, src, n, 1, 64, true, &pl->a, &pl->ma, &full)) return rc;
+        // GAP-only operands = ALL the vectors of a packed collection: one sequential stream per block column (bmx_kernels6.h)
+        if (pl->a && full) { pl->path = LP_COLL; return BMX_OK; }
+        // GAP-only operands that are SOME of the vectors of a packed collection: their pieces of its column regions
+        // (k_coll_members, bmx_kernels8.h).  Sparse lists of >= 64 vectors take the row kernel instead: a member's piece
+        // of a column is ~26 bytes there, and reading them one by one (9.1 ms for 2,048 of configs[4]'s 4,096 vectors) loses
+        // to the rows of 14 columns the vectors' own tile directories give (1.7 ms, profiles/r04i)
+        if (pl->a && !(ctx->coll_members < 0 && rows) && coll_members_wanted_list(ctx, src, n)) { pl->path = LP_MEMBERS; return BMX_OK; }
+        pl->a = nullptr;
+    }
+    // many GAP-only operands: the row kernel when they are sparse, else the column-tile kernel; any other list with columns: sort + k_agg_or
+    if (n >= 64 && gap_only) pl->path = rows ? LP_ROWS : LP_TILE;
+    else if (n && ncols) pl->path = LP_SORT;
+    return BMX_OK;
+}
+
+// many SPARSE GAP-only operands: rows of 16 block columns read through the vectors' tile directories (k_agg_or_rows,
+// bmx_kernels7.h); the kernel folds the block kinds and the popcount of its result (no layout scan when every block
+// came out as a bit-block, no count pass later)
+static int or_rows_launch(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, uint32_t ncols, int opt_compress, bmx_vec* v, BlockStat* st, DevBuf& d_tab)
+{
+    int rc; std::vector<u64> tab; tab.reserve(n * 4);
+    for (size_t i = 0; i < n; ++i) {
+        const bmx_vec* o = src[i];
+        // uploaded / imported / generated vectors carry their tile directory; a RESULT vector (or a clone) gets its own the
+        // first time it is an operand here (the directory is a cache of the immutable vector's layout: logically const)
+        if (!o->d_tdir && (rc = vec_build_tdir(ctx, const_cast<bmx_vec*>(o)))) return rc;
+        if (!o->d_tdir) continue;                                          // NULL blocks only: contributes nothing
+        tab.push_back((u64)(uintptr_t)o->d_tdir); tab.push_back((u64)(uintptr_t)o->d_gaps);
+        tab.push_back((u64)(uintptr_t)o->d_desc); tab.push_back((u64)o->nblocks);
+    }
+    const u32 nops = (u32)(tab.size() / 4);
+    if ((rc = dmalloc(ctx, &d_tab.p, std::max<size_t>(tab.size() * 8, 64))) || (rc = h2d_staged(ctx, d_tab.p, tab.data(), tab.size() * 8))) return rc;
+    const size_t lds = (size_t)ORR_TILE * 8192 + 64; const u32 ntiles = (ncols + ORR_TILE - 1) / ORR_TILE;
+    auto rows = ctx->or_depth == 8 ? k_agg_or_rows<8> : k_agg_or_rows<4>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(rows, dim3(ntiles), dim3(1024), lds, ctx->stream, (const u32x4*)d_tab, nops, ncols, opt_compress | or_rows_diag_bits(), ctx->xcd_swz,
+                           v->d_bits, v->d_desc, st, FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2}, FoldOut{ctx->d_slots2, ctx->d_done2, ctx->h_small + 8});
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? BMX_OK : fail_hip(e, "bmx_agg_or (rows)", __LINE__);
+}
+
+// many GAP-only operands: column-tile kernel straight from the descriptor tables (no sort pass)
+static int or_tile_launch(bmx_ctx* ctx, const OperandTable& ops, int opt_compress, bmx_vec* v, BlockStat* st)
+{
+    const u32 ncols = ops.ncols, ntiles = (ncols + OR_TILE - 1) / OR_TILE;
+    size_t lds = (size_t)OR_TILE * 8192 + OR_TILE * 4;
+    // or_tile: 0 = single-bit fast path (default), 1 = the round-1 run code, 2 = two operands per lane per step;
+    // tuning build, or_window = -9: loads only (the memory floor of the access pattern)
+#ifdef BMX_TUNE
+    auto tiled = ctx->or_window == -9 ? (ctx->or_tile == 2 ? k_agg_or_gap_tiled<9, 2> : k_agg_or_gap_tiled<9, 1>) :
+                 ctx->or_tile == 0 ? k_agg_or_gap_tiled<1, 1> : ctx->or_tile == 2 ? k_agg_or_gap_tiled<1, 2> : k_agg_or_gap_tiled<0, 1>;
+#else
+    auto tiled = ctx->or_tile == 0 ? k_agg_or_gap_tiled<1, 1> : ctx->or_tile == 2 ? k_agg_or_gap_tiled<1, 2> : k_agg_or_gap_tiled<0, 1>;
+#endif
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tiled), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const u32 per = even_windows(ntiles, ctx->or_window <= 0 ? 0u : (u32)ctx->or_window).per;      // windows measured: no gain here
+    for (u32 t0 = 0; t0 < ntiles; t0 += per) {
+        hipLaunchKernelGGL(tiled, dim3(std::min(per, ntiles - t0)), dim3(1024), lds, ctx->stream,
+                           ops.d_descs, ops.d_nblk, (u32)ops.n, ncols, opt_compress, v->d_bits, v->d_desc, st, t0);
+        KCHK();
+    }
+    return BMX_OK;
+}
+
+// any other list: the operands of each column sorted by kind into d_rows (k_or_sort), then a wave per column (k_agg_or<2>)
+static int or_sort_launch(bmx_ctx* ctx, const OperandTable& ops, int opt_compress, bmx_vec* v, BlockStat* st, DevBuf& d_rows)
+{
+    const u32 ncols = ops.ncols, n = (u32)ops.n;
+    if (int rc = dmalloc(ctx, &d_rows.p, (size_t)ncols * (n + 2) * 8)) return rc;
+    hipLaunchKernelGGL(k_or_sort, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, ops.d_descs, ops.d_nblk, n, ncols, (u64*)d_rows);
+    size_t lds = ops.has_gap ? 4 * 2048 * 4 : 0;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_agg_or<2>), dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
+                       (const u64*)d_rows, n, ncols, opt_compress, ctx->xcd_swz, v->d_bits, v->d_desc, st);
+    KCHK();
+    return BMX_OK;
+}
+
+// SOME members of the plan's collection(s): their indices as one arg-group (d_tab), then k_coll_members
+static int list_members_launch(int mode, bmx_ctx* ctx, const ListPlan& pl, u32 ncols, int opt_compress, bmx_vec* v, BlockStat* st, DevBuf& d_tab)
+{
+    const u32* d_midx = nullptr; const CollGroup* d_groups = nullptr;
+    if (int rc = coll_members_upload(ctx, pl.ma, pl.ms, d_tab, &d_midx, &d_groups)) return rc;
+    return coll_members_launch(mode, ctx, pl.a, pl.s, d_midx, d_groups, 1u, 0u, ncols, opt_compress, nullptr, v, st);
+}
+
+// The tail of every path of a list call.  FOLD_NONE: lay the stored blocks out (result_finish synchronises).  FOLD_KINDS: the
+// kernel folded the kinds of its result -- synchronise, then result_finish_folded; FOLD_COUNT: ... and its popcount (h_small[8]).
+// After a failed launch: wait for what it left on the stream.  Then the result is handed over.  The caller's scope-owned temporaries
+// (tables, pipeline, the pin of its collections) go behind that wait; nothing waits after result_finish, for the reason written there.
+enum { FOLD_NONE, FOLD_KINDS, FOLD_COUNT };
+static int list_finish(bmx_ctx* ctx, int rc, int fold, Owned<bmx_vec>& v, BlockStat* st, u32* offs, bmx_vec** result, int* any)
+{
+    if (rc || fold != FOLD_NONE) {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, fold == FOLD_COUNT ? "bmx_agg_or (rows)" : "k_coll_apply", __LINE__);
+    }
+    if ((rc = fold != FOLD_NONE ? result_finish_folded(ctx, v.get(), st, offs) : result_finish(ctx, v.get(), st, offs))) return rc;
+    if (fold == FOLD_COUNT) { v->count = ctx->h_small[8]; v->count_valid = true; }
+    if (any) *any = vec_any_block(v.get());
+    *result = v.release();
+    return BMX_OK;
+}
+
+static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int opt_compress, bmx_vec** result)
+{
+    ARGCHK(ctx && result && (n == 0 || src) && n <= 65535);
+    *result = nullptr;
+    int rc = set_dev(ctx); if (rc) return rc;
+    OperandTable ops; ListPlan pl;
+    if ((rc = operand_list(ctx, src, n, nullptr, 0, false, &ops))) return rc;
+    const uint32_t ncols = ops.ncols;
+    Owned<bmx_vec> v; BlockStat* st; u32* offs;
+    if ((rc = result_begin(ctx, ops.nbits, ncols, &v, &st, &offs))) return rc;  // empty list => cleared target (:1105)
+    if ((rc = agg_or_choose(ctx, src, n, ops, &pl))) return rc;
+    CollPin pin; pin.pin(pl.a);                                // (coll_members_upload allocates: the collection must outlive it)
+    // whole collection: without opt_compress no GAP block can come out: the kernel folds the kind counts of its result itself and,
+    // when every block turned out to be a bit-block (the OR of thousands of sparse vectors), the layout scan is skipped (one launch
+    // window only: the fold's tickets count the workgroups of ONE launch)
+    const bool fold = !opt_compress && ctx->coll_window == 0;
+    DevBuf d_rows(ctx), d_tab(ctx);                            // (given back in reverse: the table, then the rows)
+    switch (pl.path) {
+    case LP_DIRECT: if (!(rc = direct_table(ctx, &ops, d_tab))) rc = direct_launch(DIRECT_OR, ctx, ops, n, 0, 0u, ncols, opt_compress, v.get(), st, 0, 0u, 0u); break;
+    case LP_MEMBERS: rc = list_members_launch(CM_OR_STORE, ctx, pl, ncols, opt_compress, v.get(), st, d_tab); break;
+    case LP_COLL:
+        rc = coll_launch(COLL_OR, ctx, pl.a, nullptr, 0u, ncols, opt_compress, nullptr, v.get(), st, 0u, 0xFFFFFFFFu,
+                         fold ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr});
+        break;
+    case LP_ROWS: rc = or_rows_launch(ctx, src, n, ncols, opt_compress, v.get(), st, d_tab); break;
+    case LP_TILE: if (!(rc = direct_table(ctx, &ops, d_tab))) rc = or_tile_launch(ctx, ops, opt_compress, v.get(), st); break;
+    case LP_SORT: if (!(rc = direct_table(ctx, &ops, d_tab))) rc = or_sort_launch(ctx, ops, opt_compress, v.get(), st, d_rows); break;
+    default: break;                                            // no operand has a block: the cleared target
+    }
+    return list_finish(ctx, rc, pl.path == LP_ROWS ? FOLD_COUNT : pl.path == LP_COLL && fold ? FOLD_KINDS : FOLD_NONE, v, st, offs, result, nullptr);
 }
 
 int bmx_agg_or(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, bmx_vec** result)
@@ -3382,129 +3531,6 @@ int bmx_agg_or_opt(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int opt_co
 { ABI_TRY
     return agg_or_impl(ctx, src, n, opt_compress ? 1 : 0, result);
 ABI_END }
-
-static int agg_or_impl(bmx_ctx* ctx, const bmx_vec* const* src, size_t n, int opt_compress, bmx_vec** result)
-{
-    ARGCHK(ctx && result && (n == 0 || src) && n <= 65535);
-    *result = nullptr;
-    int rc = set_dev(ctx); if (rc) return rc;
-    OperandTable ops;
-    if ((rc = operand_list(ctx, src, n, nullptr, 0, false, &ops))) return rc;
-    const uint32_t ncols = ops.ncols; const bool has_gap = ops.has_gap, has_bit = ops.has_bit;
-    Owned<bmx_vec> v; BlockStat* st; u32* offs;
-    bmx_coll* packed = nullptr; std::vector<u32> members; bool packed_full = false;
-    CollPin pin;
-    if ((rc = result_begin(ctx, ops.nbits, ncols, &v, &st, &offs))) return rc;  // empty list => cleared target (:1105)
-    if (use_direct(ctx, ncols, n)) {
-        DevBuf d_tab(ctx);
-        if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
-        rc = direct_launch(DIRECT_OR, ctx, ops, n, 0, 0u, ncols, opt_compress, v.get(), st, 0, 0u, 0u);
-        if (!rc) rc = result_finish(ctx, v.get(), st, offs);
-        else (void)hipStreamSynchronize(ctx->stream);
-        d_tab.reset();
-        if (rc) return rc;
-    } else if (n >= 16 && ncols && has_gap && !has_bit && (rc = coll_resolve(ctx, src, n, 1, 64, true, &packed, &members, &packed_full)) == BMX_OK && packed && !packed_full &&
-               !(ctx->coll_members < 0 && n >= 64 && or_rows_wanted(ctx, src, n)) && coll_members_wanted_list(ctx, src, n)) {
-        pin.pin(packed);                                       // (coll_members_upload allocates: the collection must outlive it)
-        // GAP-only operands that are SOME of the vectors of a packed collection: their pieces of its column regions
-        // (k_coll_members, bmx_kernels8.h).  Sparse lists of >= 64 vectors take the row kernel below instead: a member's piece
-        // of a column is ~26 bytes there, and reading them one by one (9.1 ms for 2,048 of configs[4]'s 4,096 vectors) loses
-        // to the rows of 14 columns the vectors' own tile directories give (1.7 ms, profiles/r04i)
-        DevBuf d_buf(ctx); const u32* d_midx = nullptr; const CollGroup* d_groups = nullptr;
-        if ((rc = coll_members_upload(ctx, members, std::vector<u32>(), d_buf, &d_midx, &d_groups))) return rc;
-        rc = coll_members_launch(CM_OR_STORE, ctx, packed, nullptr, d_midx, d_groups, 1u, 0u, ncols, opt_compress, nullptr, v.get(), st);
-        if (!rc) rc = result_finish(ctx, v.get(), st, offs);
-        else (void)hipStreamSynchronize(ctx->stream);
-        d_buf.reset();
-        if (rc) return rc;
-    } else if (rc) { return rc;
-    } else if (packed && packed_full) {
-        pin.pin(packed);
-        // GAP-only operands = ALL the vectors of a packed collection: one sequential stream per block column (bmx_kernels6.h)
-        // without opt_compress no GAP block can come out: the kernel folds the kind counts of its result itself and, when every
-        // block turned out to be a bit-block (the OR of thousands of sparse vectors), the layout scan is skipped (one launch
-        // window only: the fold's tickets count the workgroups of ONE launch)
-        const bool fold = !opt_compress && ctx->coll_window == 0;
-        rc = coll_launch(COLL_OR, ctx, packed, nullptr, 0u, ncols, opt_compress, nullptr, v.get(), st, 0u, 0xFFFFFFFFu,
-                         fold ? FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2} : FoldOut{nullptr, nullptr, nullptr});
-        if (!rc && fold) {
-            hipError_t e = hipStreamSynchronize(ctx->stream);
-            rc = e == hipSuccess ? result_finish_folded(ctx, v.get(), st, offs) : fail_hip(e, "k_coll_apply", __LINE__);
-        } else if (!rc) rc = result_finish(ctx, v.get(), st, offs);
-        else (void)hipStreamSynchronize(ctx->stream);
-        if (rc) return rc;
-    } else if (rc) { return rc;
-    } else if (n >= 64 && ncols && has_gap && !has_bit && or_rows_wanted(ctx, src, n)) {
-        // many SPARSE GAP-only operands: rows of 16 block columns read through the vectors' tile directories (k_agg_or_rows,
-        // bmx_kernels7.h); the kernel folds the block kinds and the popcount of its result (no layout scan when every block
-        // came out as a bit-block, no count pass later)
-        std::vector<u64> tab; tab.reserve(n * 4);
-        for (size_t i = 0; i < n; ++i) {
-            const bmx_vec* o = src[i];
-            // uploaded / imported / generated vectors carry their tile directory; a RESULT vector (or a clone) gets its own the
-            // first time it is an operand here (the directory is a cache of the immutable vector's layout: logically const)
-            if (!o->d_tdir && (rc = vec_build_tdir(ctx, const_cast<bmx_vec*>(o)))) return rc;
-            if (!o->d_tdir) continue;                                          // NULL blocks only: contributes nothing
-            tab.push_back((u64)(uintptr_t)o->d_tdir); tab.push_back((u64)(uintptr_t)o->d_gaps);
-            tab.push_back((u64)(uintptr_t)o->d_desc); tab.push_back((u64)o->nblocks);
-        }
-        const u32 nops = (u32)(tab.size() / 4);
-        DevBuf d_tab(ctx);
-        if ((rc = dmalloc(ctx, &d_tab.p, std::max<size_t>(tab.size() * 8, 64))) || (rc = h2d_staged(ctx, d_tab.p, tab.data(), tab.size() * 8))) return rc;
-        const size_t lds = (size_t)ORR_TILE * 8192 + 64;
-        const u32 ntiles = (ncols + ORR_TILE - 1) / ORR_TILE;
-        auto rows = ctx->or_depth == 8 ? k_agg_or_rows<8> : k_agg_or_rows<4>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(rows, dim3(ntiles), dim3(1024), lds, ctx->stream, (const u32x4*)d_tab, nops, ncols, opt_compress | or_rows_diag_bits(), ctx->xcd_swz,
-                               v->d_bits, v->d_desc, st, FoldOut{ctx->d_slots, ctx->d_done, ctx->h_small + 2},
-                               FoldOut{ctx->d_slots2, ctx->d_done2, ctx->h_small + 8});
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        d_tab.reset();
-        if (e != hipSuccess) return fail_hip(e, "bmx_agg_or (rows)", __LINE__);
-        const uint64_t total = ctx->h_small[8];
-        if ((rc = result_finish_folded(ctx, v.get(), st, offs))) return rc;
-        v->count = total; v->count_valid = true;
-    } else if (n >= 64 && ncols && has_gap && !has_bit) {
-        // many GAP-only operands: column-tile kernel straight from the descriptor tables (no sort pass)
-        DevBuf d_tab(ctx);
-        if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
-        size_t lds = (size_t)OR_TILE * 8192 + OR_TILE * 4;
-        // or_tile: 0 = single-bit fast path (default), 1 = the round-1 run code, 2 = two operands per lane per step;
-        // tuning build, or_window = -9: loads only (the memory floor of the access pattern)
-        u32 ntiles = (ncols + OR_TILE - 1) / OR_TILE;
-#ifdef BMX_TUNE
-        auto tiled = ctx->or_window == -9 ? (ctx->or_tile == 2 ? k_agg_or_gap_tiled<9, 2> : k_agg_or_gap_tiled<9, 1>) :
-                     ctx->or_tile == 0 ? k_agg_or_gap_tiled<1, 1> : ctx->or_tile == 2 ? k_agg_or_gap_tiled<1, 2> : k_agg_or_gap_tiled<0, 1>;
-#else
-        auto tiled = ctx->or_tile == 0 ? k_agg_or_gap_tiled<1, 1> : ctx->or_tile == 2 ? k_agg_or_gap_tiled<1, 2> : k_agg_or_gap_tiled<0, 1>;
-#endif
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(tiled), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const u32 per = even_windows(ntiles, ctx->or_window <= 0 ? 0u : (u32)ctx->or_window).per;      // windows measured: no gain here
-        for (u32 t0 = 0; t0 < ntiles; t0 += per) {
-            hipLaunchKernelGGL(tiled, dim3(std::min(per, ntiles - t0)), dim3(1024), lds, ctx->stream,
-                               ops.d_descs, ops.d_nblk, (u32)n, ncols, opt_compress, v->d_bits, v->d_desc, st, t0);
-            KCHK();
-        }
-        if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    } else if (n && ncols) {
-        DevBuf d_dmat(ctx), d_tab(ctx);                                   // (given back in reverse: the table, then the rows)
-        if ((rc = direct_table(ctx, &ops, d_tab)) || (rc = dmalloc(ctx, &d_dmat.p, (size_t)ncols * (n + 2) * 8))) return rc;
-        hipLaunchKernelGGL(k_or_sort, dim3((ncols + 3) / 4), dim3(256), 0, ctx->stream, ops.d_descs, ops.d_nblk, (u32)n, ncols, (u64*)d_dmat);
-        size_t lds = has_gap ? 4 * 2048 * 4 : 0;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_agg_or<2>), dim3((ncols + 3) / 4), dim3(256), lds, ctx->stream,
-                           (const u64*)d_dmat, (u32)n, ncols, opt_compress, ctx->xcd_swz,
-                           v->d_bits, v->d_desc, st);
-        KCHK();
-        if ((rc = result_finish(ctx, v.get(), st, offs))) return rc;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-    *result = v.release();
-    return BMX_OK;
-}
 
 } // extern "C"
 
@@ -3572,91 +3598,67 @@ static int agg_and_sub_launch(bmx_ctx* ctx, const bmx_pipeline* p, uint32_t g, b
     return e == hipSuccess ? BMX_OK : fail_hip(e, what, __LINE__);
 }
 
-// The tail of every path of bmx_agg_and_sub: lay the stored blocks out (result_finish synchronises), or wait for what a failed launch
-// left on the stream; then hand the result over.  The caller's scope-owned temporaries (tables, pipeline) go behind that wait.
-static int agg_and_sub_finish(bmx_ctx* ctx, int rc, Owned<bmx_vec>& v, BlockStat* st, u32* offs, bmx_vec** result, int* any)
+extern "C" {
+
+// The path of a (non-empty) AND list with its SUB list, over ncols block columns
+static int agg_and_sub_choose(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and, const bmx_vec* const* src_sub, size_t n_sub, uint32_t ncols, ListPlan* pl)
 {
-    if (!rc) rc = result_finish(ctx, v.get(), st, offs); else (void)hipStreamSynchronize(ctx->stream);
-    if (rc) return rc;
-    if (any) *any = vec_any_block(v.get());
-    *result = v.release();
+    // small collection (few columns, many operands): one launch straight from the descriptor tables (k_direct)
+    if (use_direct(ctx, ncols, n_and + n_sub)) { pl->path = LP_DIRECT; return BMX_OK; }
+    pl->path = LP_PIPELINE; if (!ncols) return BMX_OK;
+    // GAP-only operands held by packed collections: the whole column regions (the lists name every vector of their
+    // collections, bmx_kernels6.h) or the lists' pieces of them (k_coll_members, bmx_kernels8.h)
+    bool full = false;
+    if (int rc = coll_resolve_and_sub(ctx, src_and, n_and, src_sub, n_sub, &pl->a, &pl->s, &pl->ma, &pl->ms, &full)) return rc;
+    if (pl->a && !full && !coll_members_wanted_list(ctx, src_and, n_and, src_sub, n_sub)) pl->a = pl->s = nullptr;
+    if (pl->a) pl->path = full ? LP_COLL : LP_MEMBERS;
     return BMX_OK;
 }
-
-extern "C" {
 
 int bmx_agg_and_sub(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n_and,
                     const bmx_vec* const* src_sub, size_t n_sub, bmx_vec** result, int* any)
 { ABI_TRY
     ARGCHK(ctx && result && (n_and == 0 || src_and) && (n_sub == 0 || src_sub));
-    *result = nullptr;
-    if (any) *any = 0;
+    *result = nullptr; if (any) *any = 0;
     int rc = set_dev(ctx); if (rc) return rc;
-    uint64_t nbits = 0; uint32_t ncols = 0;
-    for (size_t i = 0; i < n_and; ++i) { ARGCHK(src_and[i]); nbits = std::max(nbits, src_and[i]->nbits); ncols = std::max(ncols, src_and[i]->nblocks); }
-    for (size_t i = 0; i < n_sub; ++i) { ARGCHK(src_sub[i]); nbits = std::max(nbits, src_sub[i]->nbits); ncols = std::max(ncols, src_sub[i]->nblocks); }
-    if (!n_and) return vec_all_null(ctx, nbits, ncols, result);     // empty AND group => cleared target (:1170-1174)
+    if (!n_and) {               // empty AND group => cleared target (:1170-1174), as large as the SUB list: only a null entry is refused
+        uint64_t nbits = 0; uint32_t ncols = 0;
+        for (size_t i = 0; i < n_sub; ++i) { ARGCHK(src_sub[i]); nbits = std::max(nbits, src_sub[i]->nbits); ncols = std::max(ncols, src_sub[i]->nblocks); }
+        return vec_all_null(ctx, nbits, ncols, result);
+    }
+    OperandTable ops; ListPlan pl;
+    if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = agg_and_sub_choose(ctx, src_and, n_and, src_sub, n_sub, ops.ncols, &pl))) return rc;
+    const uint32_t ncols = ops.ncols;
+    CollPin pin; pin.pin(pl.a, pl.s);                          // (result_begin / coll_members_upload allocate: no eviction from under the call)
+    // the table of the path, then the result: the operand table of k_direct, the rows of a one-group pipeline; member indices come after
+    DevBuf d_tab(ctx); Owned<bmx_pipeline> p;
+    if (pl.path == LP_DIRECT) rc = direct_table(ctx, &ops, d_tab);
+    else if (pl.path == LP_PIPELINE) {
+        uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub; bmx_pipeline* praw = nullptr;
+        rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw); p.reset(praw);
+    }
     Owned<bmx_vec> v; BlockStat* st; u32* offs;
-    // small collection (few columns, many operands): one launch straight from the descriptor tables (k_direct)
-    if (use_direct(ctx, ncols, n_and + n_sub)) {
-        OperandTable ops; DevBuf d_tab(ctx);
-        if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = direct_table(ctx, &ops, d_tab))) return rc;
-        if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-        rc = direct_launch(DIRECT_AND_SUB, ctx, ops, n_and, n_sub, 0u, ncols, 1, v.get(), st, 0, 0u, 0u);
-        return agg_and_sub_finish(ctx, rc, v, st, offs, result, any);
+    if (rc || (rc = result_begin(ctx, ops.nbits, ncols, &v, &st, &offs))) return rc;
+    switch (pl.path) {
+    case LP_DIRECT: rc = direct_launch(DIRECT_AND_SUB, ctx, ops, n_and, n_sub, 0u, ncols, 1, v.get(), st, 0, 0u, 0u); break;
+    case LP_COLL: rc = coll_launch(COLL_AND_STORE, ctx, pl.a, pl.s, 0u, ncols, 1, nullptr, v.get(), st, 0u, 0xFFFFFFFFu); break;
+    case LP_MEMBERS: rc = list_members_launch(CM_AND_STORE, ctx, pl, ncols, 1, v.get(), st, d_tab); break;
+    default: if (ncols) rc = agg_and_sub_launch(ctx, p.get(), 0u, v.get(), st, 0u, 0xFFFFFFFFu, true); break;
     }
-    {
-        // GAP-only operands held by packed collections: the whole column regions (the lists name every vector of their
-        // collections, bmx_kernels6.h) or the lists' pieces of them (k_coll_members, bmx_kernels8.h)
-        bmx_coll *ca = nullptr, *cs = nullptr;
-        std::vector<u32> ma, ms; bool full = false;
-        bool ok = true;
-        for (size_t i = 0; i < n_and && ok; ++i) ok = src_and[i]->ctx == ctx;
-        for (size_t i = 0; i < n_sub && ok; ++i) ok = src_sub[i]->ctx == ctx;
-        if (ok && ncols && (rc = coll_resolve_and_sub(ctx, src_and, n_and, src_sub, n_sub, &ca, &cs, &ma, &ms, &full))) return rc;
-        if (ca && !full) {
-            uint64_t gw = 0, gb = 0;
-            for (size_t i = 0; i < n_and; ++i) { gw += src_and[i]->gap_words; gb += src_and[i]->counts[BMX_GAP]; }
-            for (size_t i = 0; i < n_sub; ++i) { gw += src_sub[i]->gap_words; gb += src_sub[i]->counts[BMX_GAP]; }
-            if (!coll_members_wanted(ctx, gw, gb, n_and + n_sub, 1)) ca = nullptr;
-        }
-        if (ca) {
-            CollPin pin; pin.pin(ca, cs);                      // (result_begin / coll_members_upload allocate: no eviction from under the call)
-            if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-            DevBuf d_buf(ctx);
-            if (full) rc = coll_launch(COLL_AND_STORE, ctx, ca, cs, 0u, ncols, 1, nullptr, v.get(), st, 0u, 0xFFFFFFFFu);
-            else {
-                const u32* d_midx = nullptr; const CollGroup* d_groups = nullptr;
-                rc = coll_members_upload(ctx, ma, ms, d_buf, &d_midx, &d_groups);
-                if (!rc) rc = coll_members_launch(CM_AND_STORE, ctx, ca, cs, d_midx, d_groups, 1u, 0u, ncols, 1, nullptr, v.get(), st);
-            }
-            return agg_and_sub_finish(ctx, rc, v, st, offs, result, any);
-        }
-    }
-    uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub; bmx_pipeline* praw = nullptr;
-    if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw))) return rc;
-    Owned<bmx_pipeline> p(praw);
-    if ((rc = result_begin(ctx, nbits, ncols, &v, &st, &offs))) return rc;
-    if (ncols) rc = agg_and_sub_launch(ctx, p.get(), 0u, v.get(), st, 0u, 0xFFFFFFFFu, true);
-    return agg_and_sub_finish(ctx, rc, v, st, offs, result, any);
+    return list_finish(ctx, rc, FOLD_NONE, v, st, offs, result, any);
 ABI_END }
+
+// the OR target of a results run: the input target OR every group result that is not NULL, optimised at the end (:1440-1447)
+static int or_target_run(bmx_ctx* ctx, const bmx_vec* or_target_in, const std::vector<Owned<bmx_vec>>& res, bmx_vec** or_target_out)
+{
+    std::vector<const bmx_vec*> src;
+    if (or_target_in) src.push_back(or_target_in);
+    for (const Owned<bmx_vec>& r : res) if (r) src.push_back(r.get());
+    *or_target_out = nullptr;
+    return agg_or_impl(ctx, src.data(), src.size(), 1, or_target_out);
+}
 
 // combine_and_sub(pipe) with result vectors / counts / OR target (src/bmaggregator.h:1292-1449)
-static int run_results_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, bmx_vec** results_out, uint64_t* counts_out,
-                            const bmx_vec* or_target_in, bmx_vec** or_target_out);
-
-int bmx_pipeline_run_results(bmx_ctx* ctx, bmx_pipeline* p, bmx_vec** results_out, uint64_t* counts_out,
-                             const bmx_vec* or_target_in, bmx_vec** or_target_out)
-{ ABI_TRY
-    return run_results_impl(ctx, p, 0u, 0xFFFFFFFFu, results_out, counts_out, or_target_in, or_target_out);
-ABI_END }
-
-int bmx_pipeline_run_results_range(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, bmx_vec** results_out,
-                                   uint64_t* counts_out, const bmx_vec* or_target_in, bmx_vec** or_target_out)
-{ ABI_TRY
-    return run_results_impl(ctx, p, nb_from, nb_to, results_out, counts_out, or_target_in, or_target_out);
-ABI_END }
-
 static int run_results_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, bmx_vec** results_out, uint64_t* counts_out,
                             const bmx_vec* or_target_in, bmx_vec** or_target_out)
 {
@@ -3688,16 +3690,22 @@ static int run_results_impl(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uin
         res[g] = std::move(v);
         if (counts_out && (rc = bmx_count(ctx, res[g].get(), &counts_out[g]))) return rc;
     }
-    if (or_target_out) {
-        std::vector<const bmx_vec*> src;
-        if (or_target_in) src.push_back(or_target_in);
-        for (const Owned<bmx_vec>& r : res) if (r) src.push_back(r.get());
-        *or_target_out = nullptr;
-        if ((rc = agg_or_impl(ctx, src.data(), src.size(), 1 /* optimised at the end, :1440-1447 */, or_target_out))) return rc;
-    }
+    if (or_target_out && (rc = or_target_run(ctx, or_target_in, res, or_target_out))) return rc;
     if (results_out) for (uint32_t g = 0; g < p->ngroups; ++g) results_out[g] = res[g].release();
     return BMX_OK;
 }
+
+int bmx_pipeline_run_results(bmx_ctx* ctx, bmx_pipeline* p, bmx_vec** results_out, uint64_t* counts_out,
+                             const bmx_vec* or_target_in, bmx_vec** or_target_out)
+{ ABI_TRY
+    return run_results_impl(ctx, p, 0u, 0xFFFFFFFFu, results_out, counts_out, or_target_in, or_target_out);
+ABI_END }
+
+int bmx_pipeline_run_results_range(bmx_ctx* ctx, bmx_pipeline* p, uint32_t nb_from, uint32_t nb_to, bmx_vec** results_out,
+                                   uint64_t* counts_out, const bmx_vec* or_target_in, bmx_vec** or_target_out)
+{ ABI_TRY
+    return run_results_impl(ctx, p, nb_from, nb_to, results_out, counts_out, or_target_in, or_target_out);
+ABI_END }
 
 // ---- pipelines with search masks under aggregator::set_range_hint(from, to) ----
 // The reference evaluates only the block columns of the hint (src/bmaggregator.h:1312-1346) and, when both ends lie in ONE
@@ -3750,13 +3758,7 @@ int bmx_pipeline_run_results_hint(bmx_ctx* ctx, bmx_pipeline* p, uint64_t from, 
         if (counts_out) rc = bmx_count(ctx, m, &counts_out[g]);
     }
     mask.reset();
-    if (!rc && or_target_out) {
-        std::vector<const bmx_vec*> src;
-        if (or_target_in) src.push_back(or_target_in);
-        for (const Owned<bmx_vec>& r : res) if (r) src.push_back(r.get());
-        *or_target_out = nullptr;
-        rc = agg_or_impl(ctx, src.data(), src.size(), 1, or_target_out);
-    }
+    if (!rc && or_target_out) rc = or_target_run(ctx, or_target_in, res, or_target_out);
     if (rc) return rc;
     if (results_out) for (uint32_t g = 0; g < p->ngroups; ++g) results_out[g] = res[g].release();
     return BMX_OK;
@@ -3802,11 +3804,9 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     int rc = set_dev(ctx); if (rc) return rc;
     if (!n_and) return BMX_OK;
     if (ranged && from > to) { g_last_error = "range hint: from > to"; return BMX_ERR_RANGE; }
-    uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub;
-    u32 ncols_all = 0;
-    for (size_t i = 0; i < n_and; ++i) { ARGCHK(src_and[i]); ncols_all = std::max(ncols_all, src_and[i]->nblocks); }
-    for (size_t i = 0; i < n_sub; ++i) { ARGCHK(src_sub[i]); ncols_all = std::max(ncols_all, src_sub[i]->nblocks); }
-    u32 col_from = 0, col_to = ncols_all; int has_mask = 0; u32 mf = 0, mt = 65535u;
+    OperandTable ops;
+    if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops))) return rc;
+    const u32 ncols_all = ops.ncols; u32 col_from = 0, col_to = ncols_all; int has_mask = 0; u32 mf = 0, mt = 65535u;
     if (ranged) {
         uint64_t nbf = from >> 16, nbt = to >> 16;
         col_from = (u32)std::min<uint64_t>(nbf, ncols_all);
@@ -3824,13 +3824,13 @@ static int find_first_impl(bmx_ctx* ctx, const bmx_vec* const* src_and, size_t n
     if (direct) {
         // many operands: a workgroup of 8 waves per column straight from the descriptor tables (k_direct); 64 columns first
         // (a hit in the first blocks is answered after ~1/8 of what two workgroups per CU would read)
-        OperandTable ops; DevBuf d_tab(ctx);
-        if ((rc = operand_list(ctx, src_and, n_and, src_sub, n_sub, false, &ops)) || (rc = direct_table(ctx, &ops, d_tab))) return rc;
+        DevBuf d_tab(ctx);
+        if ((rc = direct_table(ctx, &ops, d_tab))) return rc;
         return first_hit_run(ctx, "bmx_find_first_and_sub", col_from, col_to, n_and + n_sub < 24u ? 512u : 64u, [&](u32 c0, u32 c1) {
             return direct_launch(DIRECT_FIND_FIRST, ctx, ops, n_and, n_sub, c0, c1, 0, nullptr, nullptr, has_mask, mf, mt);
         }, found, idx);
     }
-    bmx_pipeline* praw = nullptr;
+    uint32_t an = (uint32_t)n_and, sn = (uint32_t)n_sub; bmx_pipeline* praw = nullptr;
     if ((rc = bmx_pipeline_create(ctx, src_and, &an, src_sub, &sn, 1, &praw))) return rc;
     Owned<bmx_pipeline> p(praw);
     const size_t lds = p->has_gap ? 4 * 2048 * 4 : 0;

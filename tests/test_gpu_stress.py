@@ -538,19 +538,66 @@ def test_device_allocation_failures_come_back_as_status(port):
     def scan_mismatch_remap():
         ok = np.array_equal(bm.sparse_vector_find_mismatch(sc_a, sc_b, bm.NO_NULL).to_indices(), exp_mm)
         return ok and np.array_equal(bm.set2set_11_transform(c).remap(vs[4], sc_a).to_indices(), exp_image)
-    for name, fn in (("pairwise", pairwise), ("combine_or", combine_or), ("rs_index", rs_index), ("prepare", prepare), ("pipeline", pipeline),
-                     ("pipeline_staged", pipeline_staged), ("pipeline_limit_dev", pipeline_limit_dev), ("op2_async", op2_async),
-                     ("and_sub_materialised", and_sub_materialised), ("upload_gap", upload_gap), ("distance_gap", distance_gap),
-                     ("pipeline_coll_served", pipeline_coll_served), ("scan_gt_vector", scan_gt_vector), ("scan_range_count", scan_range_count),
-                     ("scan_eq_counts", scan_eq_counts), ("scan_eq_keys", scan_eq_keys), ("scan_range_counts", scan_range_counts),
-                     ("scan_mismatch_remap", scan_mismatch_remap)):
+    # the list calls of the aggregator down every path that does not go through k_direct: 64 GAP-only vectors (the smallest list
+    # the row and the column-tile kernel take; 63 of them: the sort pass and k_agg_or<2>), each OR-ed with one common set so that
+    # the AND results are not empty; in a context of its own (c2) the same 64 prepared as a collection in both roles: the whole
+    # collection (kinds folded), 40 of its members, and the two AND-SUB forms of each.  A family names the context it runs in
+    common = np.unique(np.random.default_rng(64).integers(0, nbits, size=100, dtype=np.uint64))
+    cw = np.zeros(((nbits + 63) // 64) * 2, np.uint32)
+    np.bitwise_or.at(cw, (common >> np.uint64(5)).astype(np.int64), np.uint32(1) << (common & np.uint64(31)).astype(np.uint32))
+    p64 = [port.import_words(port.gen_words(5, 100 + i, 66, nbits) | cw, True, nbits) for i in range(64)]
+    c2 = bm.context(0)
+    agg2 = bm.aggregator(c2)
+    def sparse64(cx):
+        cv = bm.bvector.from_indices(cx, common, nbits, optimize=True)
+        gv = [bm.bvector.bit_or(bm.bvector.generate(cx, 5, 100 + i, 66, nbits), cv, bm.opt_compress) for i in range(64)]
+        info = [g.info() for g in gv]                    # what the selection reads: GAP blocks, no bit-block, 30 block columns
+        assert all(i["counts"][bm.BIT] == 0 and i["counts"][bm.GAP] and i["nblocks"] == 30 for i in info)
+        return gv
+    g64, h64 = sparse64(c), sparse64(c2)
+    c2.collection_prepare(h64, bm.ROLE_OR); c2.collection_prepare(h64, bm.ROLE_AND)
+    assert c2.pack_stats()["collections"] == 2
+    DEFAULTS = {"direct_cols": 384, "or_rows": -1, "coll_members": -1}
+    def tuned(cx, keys, call):
+        """call() under the tuning keys given; every one of them is put back, whatever came of the call"""
+        for key, x in keys: cx.set_tuning(key, x)
+        try:
+            return call()
+        finally:
+            for key, _ in keys: cx.set_tuning(key, DEFAULTS[key])
+    exp_or64, exp_or63, exp_or40 = port.agg_or(p64).count(), port.agg_or(p64[:63]).count(), port.agg_or(p64[:40]).count()
+    exp_and64, exp_and40 = port.agg_and_sub(p64).count(), port.agg_and_sub(p64[:40], p64[48:56]).count()
+    exp_first = port.find_first_and_sub(p64[:40], [pv[2]])
+    assert exp_and64 >= common.size and exp_first[0]
+    def or_rows(): return tuned(c, (("direct_cols", 0), ("or_rows", 1)), lambda: agg.combine_or(g64).count() == exp_or64)
+    def or_tile(): return tuned(c, (("direct_cols", 0), ("or_rows", 0)), lambda: agg.combine_or(g64).count() == exp_or64)
+    def or_sort(): return tuned(c, (("direct_cols", 0),), lambda: agg.combine_or(g64[:63]).count() == exp_or63)
+    def or_coll(): return tuned(c2, (("direct_cols", 0),), lambda: agg2.combine_or(h64).count() == exp_or64)
+    def or_members(): return tuned(c2, (("direct_cols", 0), ("coll_members", 1)), lambda: agg2.combine_or(h64[:40]).count() == exp_or40)
+    def and_sub(a, s, exp):
+        t, any_ = agg2.combine_and_sub(a, s)
+        return t.count() == exp and any_ == (exp != 0)
+    def and_coll(): return tuned(c2, (("direct_cols", 0),), lambda: and_sub(h64, [], exp_and64))
+    def and_members(): return tuned(c2, (("direct_cols", 0), ("coll_members", 1)), lambda: and_sub(h64[:40], h64[48:56], exp_and40))
+    def first_hit(): return tuple(agg.find_first_and_sub(g64[:40], [vs[2]])) == tuple(exp_first)
+    def first_direct(): return tuned(c, (("direct_cols", 384),), first_hit)
+    def first_pipeline(): return tuned(c, (("direct_cols", 0),), first_hit)
+    for name, fn, *own in (("pairwise", pairwise), ("combine_or", combine_or), ("rs_index", rs_index), ("prepare", prepare), ("pipeline", pipeline),
+                           ("pipeline_staged", pipeline_staged), ("pipeline_limit_dev", pipeline_limit_dev), ("op2_async", op2_async),
+                           ("and_sub_materialised", and_sub_materialised), ("upload_gap", upload_gap), ("distance_gap", distance_gap),
+                           ("pipeline_coll_served", pipeline_coll_served), ("scan_gt_vector", scan_gt_vector), ("scan_range_count", scan_range_count),
+                           ("scan_eq_counts", scan_eq_counts), ("scan_eq_keys", scan_eq_keys), ("scan_range_counts", scan_range_counts),
+                           ("scan_mismatch_remap", scan_mismatch_remap), ("or_rows", or_rows, c), ("or_tile", or_tile, c), ("or_sort", or_sort, c),
+                           ("or_coll", or_coll, c2), ("or_members", or_members, c2), ("and_coll", and_coll, c2), ("and_members", and_members, c2),
+                           ("first_direct", first_direct, c), ("first_pipeline", first_pipeline, c)):
+        cx = own[0] if own else c
         assert fn(), name                                 # warm: pooled blocks, scratch sized
-        c.synchronize(); c.trim()
-        base = c.mem_used()
+        cx.synchronize(); cx.trim()
+        base, colls = cx.mem_used(), cx.pack_stats()["collections"]
         for kind in (4, 6):
             failed = 0
             for k in range(0, 40):
-                c.inject_failure(kind, k)
+                cx.inject_failure(kind, k)
                 try:
                     ok = fn()
                     assert ok, (name, kind, k)
@@ -558,11 +605,13 @@ def test_device_allocation_failures_come_back_as_status(port):
                     assert e.status == 1, (name, kind, k, str(e))
                     failed += 1
                 finally:
-                    c.inject_failure(0, 0)
-                c.synchronize()
+                    cx.inject_failure(0, 0)
+                cx.synchronize()
             assert fn(), (name, kind)
-            c.synchronize()
+            cx.synchronize()
             assert failed >= 1, (name, kind)              # (every one of these calls allocates at least once)
-        leaked = c.mem_used() - base
+        leaked = cx.mem_used() - base
         assert leaked <= (2 << 20), (name, leaked)        # (pool rounding of a fresh result may differ; a lost slab would be MBs per failure)
+        if own: assert cx.pack_stats()["collections"] == colls, name      # (the list families: stays at what was prepared)
+    h64.clear(); c2.close()
     c.close()
